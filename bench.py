@@ -9,6 +9,12 @@ r = 0.05, L2, int32 indices.  One step = the full Open3D
 scan + host read of the total + fill.  Inputs are resident in HBM before the
 timed region.  value = queries processed by all ranks / wall time (Mpoints/s).
 
+A plain run does that and nothing else: set-up, `--warmup` steps, `--steps`
+timed steps, the result line (ms_per_step = the timed wall time / `--steps`).
+`--dump-outputs DIR` also writes what the last timed step returned (see
+dump_outputs).  Everything below (roofline, cpu_baseline, the size sweep and
+the C2..C5 model legs) is measured only with `--full`, after the timed steps.
+
 Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) every rank
 is one of its processes; `python bench.py --gpus N` without torchrun spawns
 the N processes itself (torch.multiprocessing, 'spawn' start method, before
@@ -59,6 +65,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scenes", type=int, default=64, help="C1-shaped scenes per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline C1 run, also measure everything else (per-kernel roofline, CPU "
+                         "baselines, C1 size sweep, C2..C5 models, per-op rooflines); the options below select "
+                         "within it and do nothing without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; a fixed "
+                         "seeded sample of the entries of an array too large to keep whole)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-reps", type=int, default=5)
     ap.add_argument("--op-reps", type=int, default=20, help="per-op roofline reps: kNN, grid subsample, voxelize "
@@ -82,6 +95,34 @@ def make_batch(rank, scenes, dev):
         for s in range(scenes)])
     rs = np.arange(scenes + 1, dtype=np.int64) * N_POINTS
     return torch.from_numpy(pts).to(dev), torch.from_numpy(rs)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all arrays of all ranks together, shared equally
+
+
+def dump_outputs(res, out_dir, rank=0, world=1):
+    """--dump-outputs: the tensors the last timed step returned (the fields of
+    layers.FixedRadiusSearch's result; an empty one is left out), DIR/<field>.npy
+    each (rank r > 0 of a multi-GPU run: <field>.rank<r>.npy).  Integer arrays
+    are written as float64 (exact), floating-point ones in their own precision.
+    An array over its share of the budget is written as a sample: its entries
+    at sorted positions drawn by a generator seeded with the array's length
+    (first and last entry included), so two builds that return arrays of the
+    same length are compared entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (len(res._fields) * world)
+    for name in res._fields:
+        t = getattr(res, name).detach().reshape(-1)
+        if t.numel() == 0:  # neighbors_distance without return_distances: nothing to compare
+            continue
+        dtype = np.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else np.float64
+        n, keep = t.numel(), share // np.dtype(dtype).itemsize
+        if n > keep:
+            pos = np.random.default_rng(n).integers(0, n, keep - 2)
+            pos = np.unique(np.concatenate([pos, [0, n - 1]]))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        arr = t.cpu().numpy().astype(dtype)
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
 
 
 KERNELS = ("frs_group_search", "frs_group_rows")
@@ -835,6 +876,47 @@ def plumbing_test(args, world, rank):
         dist.destroy_process_group()
 
 
+def full_fields(out, args, dev, world, step, ms_step, pp, sc_multi, rl_multi):
+    """--full: everything beside the headline figure, added to the result line
+    `out` on rank 0 (pp, sc_multi, rl_multi: the legs every rank has run)."""
+    pairs = out["config"]["pairs_per_step_rank0"]
+    dominant, avg, alg_bytes, mean_nbrs = kernel_profile(step, args.scenes * N_POINTS, pairs, args.kernel_reps)
+    ms = avg[dominant]
+    achieved = alg_bytes / (ms * 1e-3) / 1e9
+    step_achieved = alg_bytes / (ms_step * 1e-3) / 1e9
+    out["roofline"] = {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2),
+                       "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                       "traffic": load_traffic(dominant), "kernel_ms": round(ms, 5),
+                       "kernel_ms_all": {k: round(v, 5) for k, v in avg.items()},
+                       "alg_bytes_per_launch": int(alg_bytes), "mean_neighbors": round(mean_nbrs, 3),
+                       "issue": issue_bound(dominant),
+                       "step": {"achieved": round(step_achieved, 2), "frac": round(step_achieved / HBM_PEAK_GBS, 4),
+                                "note": "same algorithmic bytes / ms_per_step (hash build, search, "
+                                        "row copy and host gaps included)"}}
+    out["cpu_baseline"] = None
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline()
+    if world == 1 and args.sweep_reps > 0:
+        out["c1_sweep"] = c1_sweep(dev, args.sweep_reps)
+    if world == 1 and args.sparse_conv_reps > 0:
+        out["sparse_conv"] = sparse_conv_bench(dev, args.sparse_conv_reps)
+    if sc_multi is not None:
+        out["sparse_conv"] = sc_multi
+    if pp is not None:
+        out["pointpillars"] = pp
+    if world == 1 and args.kpconv_steps > 0:
+        out["kpconv"] = kpconv_bench(dev, args.kpconv_steps)
+    if world == 1 and args.randla_frames > 0:
+        out["randlanet"] = randla_frames(dev, args.randla_frames, cpu=not args.no_cpu_baseline)
+    if world == 1 and args.op_reps > 0:
+        ops_rl = op_rooflines(dev, args.op_reps)
+        out["ops_roofline"] = ops_rl
+        if "randlanet" in out:
+            out["randlanet"]["roofline"] = dict(ops_rl["knn"], op="knn (C2 dominant kernel)")
+    if rl_multi is not None:
+        out["randlanet"] = rl_multi
+
+
 def run(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -853,22 +935,22 @@ def run(args):
     elapsed, res = timed_run(step, args.steps, args.warmup, world, lambda: torch.cuda.synchronize(dev))
     pairs = int(res.neighbors_row_splits[-1].item())
     units = gather_units(args.scenes * N_POINTS * args.steps, world)
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs, rank, world)
 
-    pp = pointpillars_bench(dev, world, rank, args.pointpillars_steps) if args.pointpillars_steps > 0 else None
+    full = args.full
+    pp = pointpillars_bench(dev, world, rank, args.pointpillars_steps) \
+        if full and args.pointpillars_steps > 0 else None
     # the sharding workloads run on every rank at N > 1 (collective timing)
     sc_multi = sparse_conv_ranks(dev, args.sparse_conv_reps, world, rank) \
-        if world > 1 and args.sparse_conv_reps > 0 else None
+        if full and world > 1 and args.sparse_conv_reps > 0 else None
     rl_multi = randla_frames(dev, args.randla_frames, False, world, rank) \
-        if world > 1 and args.randla_frames > 0 else None
+        if full and world > 1 and args.randla_frames > 0 else None
     out = None
     if rank == 0:
         queries_total = sum(units)
         value = queries_total / elapsed / 1e6
         ms_step = elapsed / args.steps * 1e3
-        dominant, avg, alg_bytes, mean_nbrs = kernel_profile(step, args.scenes * N_POINTS, pairs, args.kernel_reps)
-        ms = avg[dominant]
-        achieved = alg_bytes / (ms * 1e-3) / 1e9
-        step_achieved = alg_bytes / (ms_step * 1e-3) / 1e9
         out = {
             "metric": "Mpoints/s neighbor-search + sparse-conv fwd; RandLA-Net frames/s",
             "value": round(value, 2),
@@ -888,38 +970,9 @@ def run(args):
                 "scenes_per_gpu": args.scenes, "points_per_scene": N_POINTS, "radius": RADIUS,
                 "pairs_per_step_rank0": pairs, "parallelism": f"scene-dp{world}",
                 "queries_per_rank": units},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": load_traffic(dominant), "kernel_ms": round(ms, 5),
-                         "kernel_ms_all": {k: round(v, 5) for k, v in avg.items()},
-                         "alg_bytes_per_launch": int(alg_bytes), "mean_neighbors": round(mean_nbrs, 3),
-                         "issue": issue_bound(dominant),
-                         "step": {"achieved": round(step_achieved, 2), "frac": round(step_achieved / HBM_PEAK_GBS, 4),
-                                  "note": "same algorithmic bytes / ms_per_step (hash build, search, "
-                                          "row copy and host gaps included)"}},
-            "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and args.sweep_reps > 0:
-            out["c1_sweep"] = c1_sweep(dev, args.sweep_reps)
-        if world == 1 and args.sparse_conv_reps > 0:
-            out["sparse_conv"] = sparse_conv_bench(dev, args.sparse_conv_reps)
-        if sc_multi is not None:
-            out["sparse_conv"] = sc_multi
-        if pp is not None:
-            out["pointpillars"] = pp
-        if world == 1 and args.kpconv_steps > 0:
-            out["kpconv"] = kpconv_bench(dev, args.kpconv_steps)
-        if world == 1 and args.randla_frames > 0:
-            out["randlanet"] = randla_frames(dev, args.randla_frames, cpu=not args.no_cpu_baseline)
-        if world == 1 and args.op_reps > 0:
-            ops_rl = op_rooflines(dev, args.op_reps)
-            out["ops_roofline"] = ops_rl
-            if "randlanet" in out:
-                out["randlanet"]["roofline"] = dict(ops_rl["knn"], op="knn (C2 dominant kernel)")
-        if rl_multi is not None:
-            out["randlanet"] = rl_multi
+        if full:
+            full_fields(out, args, dev, world, step, ms_step, pp, sc_multi, rl_multi)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

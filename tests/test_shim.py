@@ -183,3 +183,20 @@ def test_reference_checkout_through_namespace(tmp_path):
     r = _run_py(_CHECK_REFERENCE, {"OPEN3D_ML_ROOT": "/root/reference"}, str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     assert "REFERENCE NAMESPACE OK" in r.stdout
+
+
+def test_state_dict_layout_matches_recorded_reference():
+    """The same layout check without a checkout: RandLANet / SparseConvUnet /
+    KPFCNN of this build against the reference models' state_dict names and
+    shapes recorded in tests/golden/state_dicts.json (make_golden_state_dicts.py),
+    key for key and shape for shape (construction only, no compute)."""
+    import json
+    import os
+    from o3dml_amd import kpfcnn, randlanet, sparseconvnet
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "state_dicts.json")) as f:
+        recorded = json.load(f)
+    built = {"RandLANet": randlanet.RandLANet(num_points=45056, num_classes=19),
+             "SparseConvUnet": sparseconvnet.SparseConvUnet(), "KPFCNN": kpfcnn.KPFCNN()}
+    assert sorted(recorded) == sorted(built)
+    for name, m in built.items():
+        assert {k: list(v.shape) for k, v in m.state_dict().items()} == recorded[name], name

@@ -12,9 +12,9 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-me
 tail -1 "$OUT/pytest_gpu.log"
 timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { echo "smoke rc=$?"; exit 1; }
 tail -1 "$OUT/smoke.log"
-timeout -k 10 500 python bench.py > "$OUT/full_bench.log" 2>&1 || { echo "bench rc=$?"; tail -5 "$OUT/full_bench.log"; exit 1; }
+timeout -k 10 500 python bench.py --full > "$OUT/full_bench.log" 2>&1 || { echo "bench rc=$?"; tail -5 "$OUT/full_bench.log"; exit 1; }
 tail -1 "$OUT/full_bench.log" | cut -c1-300
-TAG=$T/frs bash tools/round_profile.sh || exit 1
+OUT_DIR=$(dirname "$OUT") TAG=$T/frs bash tools/round_profile.sh || exit 1
 for s in kpconv pp randla; do SECTION=$s TAG=$T bash tools/prof_section.sh || exit 1; done
 (cd /tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/scn" -o run --output-format csv \
     -- python3 "$R/tools/scn_frames.py" 10 > "$OUT/scn.log" 2>&1) || { echo "scn rc=$?"; exit 1; }

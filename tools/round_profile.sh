@@ -1,11 +1,11 @@
 #!/bin/bash
 # Round profile: bench line + rocprofv3 kernel stats of the same command + PMC
 # HBM passes (FETCH_SIZE and WRITE_SIZE in separate passes, kernel-trace only)
-# -> gpurun_out/$TAG/.  Copy the summaries into profiles/<round>/ afterwards
+# -> $OUT_DIR/$TAG/ (OUT_DIR: default out/ in the tree).  Copy the summaries into profiles/<round>/ afterwards
 # (tools/pmc_traffic.py writes the traffic JSON bench.py reads).
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 ROOTDIR=$(pwd)
-OUT=$ROOTDIR/gpurun_out/${TAG:-prof}
+OUT=${OUT_DIR:-$ROOTDIR/out}/${TAG:-prof}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 BARGS_X="--no-cpu-baseline --randla-frames 0 --sparse-conv-reps 0 --kpconv-steps 0 --pointpillars-steps 0 --sweep-reps 0"
