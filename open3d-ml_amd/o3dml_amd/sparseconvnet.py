@@ -9,6 +9,7 @@ round-trips the voxel maps through numpy, sparseconvnet.py:302-315).  One
 forward runs inside a rulebook-cache scope, so all submanifold convolutions of
 one level share one kernel map instead of rebuilding it per layer.
 """
+import operator
 import os
 
 import numpy as np
@@ -37,15 +38,19 @@ class BatchNormBlock(nn.Module):
 
 def _folded_bn(block):
     """Eval-mode BatchNorm1d of a BatchNormBlock as a per-channel affine
-    (scale, shift), cached until a parameter or buffer changes."""
+    (scale, shift), cached until a parameter or buffer changes in place
+    (version counters) or is replaced by another tensor (identity: a fresh
+    tensor starts at version 0 again)."""
     bn = block.bn
-    key = (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
-           bn.weight.device, bn.eps)
-    if getattr(block, "_fold_key", None) != key:
+    src = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    key = tuple(t._version for t in src) + (bn.weight.device, bn.eps)
+    held = getattr(block, "_fold_src", None)
+    if held is None or any(a is not b for a, b in zip(held, src)) or block._fold_key != key:
         with torch.no_grad():
             scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
             block._fold = (scale.contiguous(), (bn.bias - bn.running_mean * scale).contiguous())
         block._fold_key = key
+        block._fold_src = src
     return block._fold
 
 
@@ -784,12 +789,26 @@ class SparseConvUnet(nn.Module):
     def _param_key(self):
         """(address, version) of every parameter and buffer: a captured body
         is only replayed on the weights it was captured with.  The tensor list
-        is kept (walking the module tree costs ~1 ms per frame) and dropped by
-        _apply (.to / .cuda / .float replace the tensors)."""
-        ts = self.__dict__.get("_o3dml_state_tensors")
-        if ts is None:
-            ts = self.__dict__["_o3dml_state_tensors"] = list(self.parameters()) + list(self.buffers())
-        return tuple((t.data_ptr(), t._version) for t in ts)
+        is kept (walking the module tree costs ~1 ms per frame) with the
+        module slot each tensor came from; a slot that holds another object
+        (a new nn.Parameter or buffer assigned, load_state_dict(assign=True))
+        drops the list and every captured body, as _apply (.to / .cuda /
+        .float) and load_state_dict do."""
+        ent = self.__dict__.get("_o3dml_state_tensors")
+        if ent is not None:
+            dicts, names, held, _ = ent  # per frame: one identity test per slot, no Python-level loop
+            if not all(map(operator.is_, map(dict.get, dicts, names), held)):
+                self._invalidate_eval_caches(keep_plan=True)
+                ent = None
+        if ent is None:
+            slots = [(d, k, t) for m in self.modules() for d in (m._parameters, m._buffers) for k, t in d.items()]
+            seen, ts = set(), []
+            for _, _, t in slots:
+                if t is not None and id(t) not in seen:
+                    seen.add(id(t))
+                    ts.append(t)
+            ent = self.__dict__["_o3dml_state_tensors"] = tuple(list(c) for c in zip(*slots)) + (ts,)
+        return tuple((t.data_ptr(), t._version) for t in ent[3])
 
     _SEEN = 16  # size signatures remembered for the capture-on-second-sighting policy
 
@@ -805,14 +824,26 @@ class SparseConvUnet(nn.Module):
             seen.pop(next(iter(seen)))
         return hit
 
+    def _invalidate_eval_caches(self, keep_plan=False):
+        """Drop the kept tensor list and everything captured on the tensors it
+        names (graph bodies, the sightings) and, unless keep_plan (it holds no
+        weights, only input buffers on the model's device), the plan."""
+        for name in ("_o3dml_state_tensors", "_o3dml_scn_bodies", "_o3dml_scn_single", "_o3dml_scn_plan_bodies",
+                     "_o3dml_scn_seen"):
+            self.__dict__.pop(name, None)
+        if not keep_plan:
+            self.__dict__.pop("_o3dml_scn_plan", None)
+
     def _apply(self, fn, *args, **kwargs):
-        self.__dict__.pop("_o3dml_state_tensors", None)
-        self.__dict__.pop("_o3dml_scn_bodies", None)
-        self.__dict__.pop("_o3dml_scn_single", None)
-        self.__dict__.pop("_o3dml_scn_plan", None)
-        self.__dict__.pop("_o3dml_scn_plan_bodies", None)
-        self.__dict__.pop("_o3dml_scn_seen", None)
+        self._invalidate_eval_caches()
         return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        # assign=True replaces the tensor objects without going through _apply
+        try:
+            return super().load_state_dict(*args, **kwargs)
+        finally:
+            self._invalidate_eval_caches()
 
     def _forward_graph(self, inputs):
         """Eval forward with the body replayed from captured graphs (_ScnHead /
@@ -913,14 +944,18 @@ class SparseConvUnet(nn.Module):
         feats = inputs.feat[0]
         if pts.dtype != torch.float32 or feats.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
             return self._forward_graph_single(inputs)
-        pts, feats = pts.contiguous(), feats.contiguous()
+        if feats.dim() != 2 or feats.shape[1] < 3:
+            return self._forward_graph_single(inputs)
+        # the InputLayer averages columns 0 - 2 only (sparseconvnet.py:318-326),
+        # whatever else the feature rows carry: the plan gets those three
+        pts, feats = pts.contiguous(), (feats if feats.shape[1] == 3 else feats[:, :3]).contiguous()
         dev = pts.device
         n = int(pts.shape[0])
         cap = max(self._PLAN_STEP, -(-n // self._PLAN_STEP) * self._PLAN_STEP)
-        pk = (str(dev), cap, int(feats.shape[1]))
+        pk = (str(dev), cap, 3)
         plan = self.__dict__.get("_o3dml_scn_plan")
         if plan is None or plan[0] != pk:
-            plan = (pk, _ScnPlan(cap, int(feats.shape[1]), self.unet.n_down(), dev))
+            plan = (pk, _ScnPlan(cap, 3, self.unet.n_down(), dev))
             self.__dict__["_o3dml_scn_plan"] = plan
             self.__dict__.pop("_o3dml_scn_plan_bodies", None)  # they read the old buffers
         plan = plan[1]

@@ -22,7 +22,15 @@ C3 — KPFCNN (kpconv_s3dis.yml, first_features_dim 128) on bench.make_c3(0),
   reference's fp32 first-layer gradient is itself 4.4e-4 (eval) / 2.7e-3
   (training) off the fp64 one.
 C4 — SparseConvUnet m=32 on the 88,006-voxel room (bench.make_room(0)):
-  logits within 1e-4 of their range, column sums within 1e-5 per row."""
+  logits within 1e-4 of their range, column sums within 1e-5 per row, per
+  element |a - b| <= 1e-4 |b| + 1e-5 max|b| against the float64 run (the
+  reference's own fp32 logits sit within 2.8e-7 of it) — on the three frames
+  of the default graph mode, i.e. the path bench.py times: the first sighting
+  of the size signature (eager body on the plan's buffers), the capture frame
+  and the replay (bit-equal to the first); a fourth frame with other features
+  replays the captured body and equals the O3DML_SCN_GRAPH=0 forward bit for
+  bit.  (The training step of the same model against float64:
+  test_gpu_scn.test_scn_step_matches_reference.)"""
 import hashlib
 import os
 import sys
@@ -219,8 +227,9 @@ def test_c3_step_matches_reference(c3, mode):
             assert err < gbound(F[f"c3_{mode}_ref32_err_grad:{k}"]), (k, err)
 
 
-def test_c4_scn_full_room_vs_reference(cuda):
+def test_c4_scn_full_room_vs_reference(cuda, monkeypatch):
     import bench
+    monkeypatch.delenv("O3DML_SCN_GRAPH", raising=False)  # the default mode: what bench.py times
     from o3dml_amd.sparseconvnet import SparseConvUnet
     pos, _ = bench.make_room(0)
     assert len(pos) == int(F["c4_n"])
@@ -231,8 +240,19 @@ def test_c4_scn_full_room_vs_reference(cuda):
     m = m.to(cuda).eval()
     inp = types.SimpleNamespace(point=[torch.from_numpy(pos).to(cuda)], feat=[torch.from_numpy(feat).to(cuda)],
                                 batch_lengths=[len(pos)])
+    # three frames of the same room: the first sighting of its size signature
+    # (the eager body on the plan's buffers), the capture frame, the replay —
+    # the path behind unet.ms_per_frame
+    frames = []
     with torch.no_grad():
-        out = m(inp).cpu().numpy()
+        for j in range(3):
+            frames.append(m(inp).clone())
+            bodies = m.__dict__.get("_o3dml_scn_plan_bodies", {})
+            if j == 0:
+                assert len(bodies) == 0
+            else:
+                assert len(bodies) == 1 and all(b.graph is not None for b in bodies.values())
+    out = frames[0].cpu().numpy()
     ref = F["c4_logit_rows"]
     assert _rel(out[::11], ref) < 1e-4
     # per element against the float64 run of the same reference model:
@@ -244,3 +264,20 @@ def test_c4_scn_full_room_vs_reference(cuda):
     assert (err <= bound).all(), (float((err / bound).max()), float(err.max()))
     np.testing.assert_allclose(out.astype(np.float64).sum(0), F["c4_logit_colsum"], rtol=0,
                                atol=1e-5 * len(out) * np.abs(ref).max())
+    for j, frame in enumerate(frames[1:], 1):  # the capture frame and the replay, to the same bounds
+        o = frame.cpu().numpy()
+        err = np.abs(o[::11].astype(np.float64) - b64)
+        assert (err <= bound).all(), (j, float((err / bound).max()), float(err.max()))
+        np.testing.assert_allclose(o.astype(np.float64).sum(0), F["c4_logit_colsum"], rtol=0,
+                                   atol=1e-5 * len(o) * np.abs(ref).max())
+    assert torch.equal(frames[2], frames[0])
+    # a fourth frame with other features replays the captured body: the eager
+    # forward (O3DML_SCN_GRAPH=0) of the same input, bit for bit
+    feat2 = np.random.default_rng(4).random((len(pos), 3), dtype=np.float32)
+    inp2 = types.SimpleNamespace(point=inp.point, feat=[torch.from_numpy(feat2).to(cuda)], batch_lengths=[len(pos)])
+    with torch.no_grad():
+        replayed = m(inp2).clone()
+        assert len(m.__dict__["_o3dml_scn_plan_bodies"]) == 1  # no new capture
+        monkeypatch.setenv("O3DML_SCN_GRAPH", "0")
+        eager = m(inp2)
+    assert not torch.equal(replayed, frames[0]) and torch.equal(replayed, eager)

@@ -96,10 +96,12 @@ def reduce_subarrays_sum(values, row_splits):
 
 
 class _SparseConvStub(torch.nn.Module):
-    """Open3D layers.SparseConv restated on the oracle (CPU, forward only):
-    Linf fixed-radius neighbours of out_pos - offset*vs (radius k*vs/2), kernel
-    index per pair, oracle sparse_conv (+ bias).  Parameters kernel / bias /
-    offset as the layer's state_dict."""
+    """Open3D layers.SparseConv restated on the oracle (CPU): Linf fixed-radius
+    neighbours of out_pos - offset*vs (radius k*vs/2), kernel index per pair,
+    oracle sparse_conv (+ bias).  Parameters kernel / bias / offset as the
+    layer's state_dict.  Without autograd: the oracle's C sparse_conv
+    (float32) or detached float64 sums; with autograd on and an input that
+    requires grad: the same rulebook in torch ops (_forward_autograd)."""
     _mirror, _sign = False, 1.0
 
     def __init__(self, in_channels, filters, kernel_size, activation=None, use_bias=True, normalize=False,
@@ -120,6 +122,9 @@ class _SparseConvStub(torch.nn.Module):
         q = (op - self._sign * _np(self.offset) * vs).astype(np.float32)
         idx, rs, _ = O.fixed_radius_search(ip, q, 0.5 * vs * self.kernel_size[0], metric="Linf")
         kid = O.kernel_index(ip, q, idx, rs, self.kernel_size, vs, mirror=self._mirror)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                           for t in (inp_features, self.kernel, self.bias)):
+            return self._forward_autograd(inp_features, idx, kid, rs)
         if inp_features.dtype == torch.float64:  # float64 run: the same rulebook, float64 sums
             K = int(np.prod(self.kernel_size))
             W = self.kernel.detach().reshape(K, self.kernel.shape[-2], self.kernel.shape[-1]).double()
@@ -136,6 +141,44 @@ class _SparseConvStub(torch.nn.Module):
                                                  normalize=self.normalize))
         if self.bias is not None:
             out = out + self.bias.detach()
+        return self.activation(out) if self.activation else out
+
+    def _forward_autograd(self, inp_features, idx, kid, rs):
+        """The same rulebook in torch ops (float32 or float64, the features'
+        type), so autograd gives d/dfeatures, d/dkernel and d/dbias: one
+        product per kernel offset (never W[kid] per pair, pairs x cin x cout)
+        written to the pairs' rows, then one sum per output row in pair order,
+        as the detached float64 branch sums."""
+        dt = inp_features.dtype
+        K = int(np.prod(self.kernel_size))
+        W = self.kernel.reshape(K, self.kernel.shape[-2], self.kernel.shape[-1]).to(dt)
+        n_out = len(rs) - 1
+        cnt = torch.from_numpy(np.diff(rs).astype(np.int64))
+        o = torch.repeat_interleave(torch.arange(n_out), cnt)
+        idx_t = torch.from_numpy(np.asarray(idx)).long()
+        kid_t = torch.from_numpy(np.asarray(kid)).long()
+        order = torch.argsort(kid_t, stable=True)
+        per_k = torch.bincount(kid_t, minlength=K).tolist()
+        parts, at = [], 0
+        for k in range(K):
+            sel = order[at:at + per_k[k]]
+            at += per_k[k]
+            # batched [1, cin] x [cin, cout] products over W[k] as a stride-0 view:
+            # the detached branch's per-pair einsum bit for bit (a plain
+            # [n, cin] @ W[k] rounds differently for some cin), in slices so a
+            # copy of the view a backend makes stays small
+            step = max(1, (1 << 22) // (W.shape[1] * W.shape[2]))
+            for s in range(0, sel.numel(), step):
+                x = inp_features[idx_t[sel[s:s + step]]]
+                parts.append(torch.bmm(x[:, None, :], W[k][None].expand(x.shape[0], -1, -1))[:, 0])
+        contrib = torch.zeros((idx_t.shape[0], W.shape[-1]), dtype=dt)
+        if parts:
+            contrib = contrib.index_copy(0, order, torch.cat(parts, 0))
+        out = torch.zeros((n_out, W.shape[-1]), dtype=dt).index_add(0, o, contrib)
+        if self.normalize:
+            out = out / cnt.to(dt).clamp(min=1)[:, None]
+        if self.bias is not None:
+            out = out + self.bias.to(dt)
         return self.activation(out) if self.activation else out
 
 
