@@ -398,8 +398,9 @@ int o3dml_sparse_conv_build_map(const int32_t* neighbors_index, const int32_t* n
                                 const float* neighbors_importance, const int64_t* neighbors_row_splits, int64_t n_out,
                                 int64_t n_in, int K, int normalize, const float* out_importance, int want_inverse,
                                 int* status_host, void* workspace, size_t workspace_bytes, void* stream);
-/* split-K partial sums for the forward GEMM (deep levels with few output
- * rows split the offset x Cin reduction across waves; 0 when unsplit) */
+/* transposed filters, split-K partial sums for the forward GEMM (deep levels
+ * with few output rows split the offset x Cin reduction across waves) and the
+ * split-filter copy; n_in is unused (kept for ABI stability) */
 size_t o3dml_sparse_conv_forward_workspace_size(int64_t n_out, int64_t n_in, int K, int cin, int cout);
 int o3dml_sparse_conv_forward(const float* filters, int K, int cin, int cout, const float* inp_features, int64_t n_in,
                               const float* inp_importance, int has_neighbors_importance, int use_out_scale,
@@ -423,22 +424,16 @@ int o3dml_sparse_conv_backward(const float* filters, int K, int cin, int cout, c
                                size_t workspace_bytes, void* stream);
 /* Product precision of the sparse-conv gather-GEMMs (forward, input
  * gradient and filter gradient), all accumulating in f32:
- *   0 (default) "bf16x6": each f32 operand split into three bf16 terms
+ *   0 "bf16x6": each f32 operand split into three bf16 terms
  *     (hi + mid + lo holds all 24 mantissa bits) and the six products down to
  *     2^-16 relative taken on the bf16 MFMA pipe — the dropped terms are below
  *     the f32 rounding level;
- *   1 exact f32-input MFMA (v_mfma_f32_32x32x2_f32, bitwise an fmaf chain);
+ *   1 (default) exact f32-input MFMA (v_mfma_f32_32x32x2_f32, bitwise an fmaf
+ *     chain);
  *   2 "bf16x3": hi + mid only, three products (~2^-17 relative per product).
  * Env O3DML_SPARSE_CONV_EXACT sets the initial mode.  Returns the previous
  * mode (-1 for a mode > 2, nothing changed); exact < 0 only queries. */
 int o3dml_sparse_conv_set_exact(int exact);
-/* Operand presplit for the bf16x6 / bf16x3 products (default OFF, measured
- * slower on MI355X; see sparse_conv.hip): the hi /
- * mid / lo bf16 planes of the source rows and filters are made once per GEMM
- * (workspace from the *_workspace_size functions) and the GEMM kernel only
- * loads them; the sums are bit-identical to the in-kernel split.  on = 0 / 1
- * sets, < 0 queries; returns the previous setting. */
-int o3dml_sparse_conv_set_presplit(int on);
 /* Filters split into bf16 hi / mid / lo once per call for the narrow-output
  * GEMM (default on; same bits either way).  on < 0 only queries; returns the
  * previous setting. */

@@ -26,10 +26,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <array>
 #include <vector>
 
-#include "counters.hpp"
 #include "primitives.hpp"
 
 namespace o3dml {
@@ -129,49 +127,16 @@ static bool use_order(int64_t n, int K) {
     return on && K > 8 && n >= kOrderMinRows;
 }
 
-// Grids of the GEMM kernels.  O3DML_GEMM_XCD=1: a multiple of 8 workgroups,
-// so xcd_block() hands each XCD one contiguous range of tiles (the extra
-// workgroups exit at once).  OFF by default: same-session A/B on the C4 room
-// (tools/gemm_probe.py, with and without the chunked tile order below) was
-// neutral to 4 % slower at 32->32, 64->32 and 128->128 — the gathers' L2
-// locality is not what bounds these kernels.  Off: an odd grid, so
-// xcd_block() keeps blockIdx.x.
-static int64_t round8(int64_t g) {
-    static const bool on = [] {
-        const char* e = std::getenv("O3DML_GEMM_XCD");
-        return e ? std::atoi(e) != 0 : false;
-    }();
-    if (!on) return g | 1;  // odd: xcd_block() falls back to blockIdx.x
-    return (g + 7) & ~int64_t(7);
-}
-
-// Tile order: rows grouped by their offset mask, globally (default) or inside
-// chunks of O3DML_ORDER_CHUNK consecutive rows (rows come in voxel order, so
-// a chunk is a spatial slab that keeps a tile's or an XCD's gathers local).
-// Chunks measured neutral (4,096 rows) to 10 % slower (1,024) — kept off.
-static int order_chunk_log() {
-    static const int v = [] {
-        const char* e = std::getenv("O3DML_ORDER_CHUNK");
-        const int c = e ? std::atoi(e) : 0;
-        if (c <= 0) return 0;
-        int l = 0;
-        while ((1 << (l + 1)) <= c) ++l;
-        return l;
-    }();
-    return v;
-}
-
-// key = (chunk, hb-bit hash of the offset mask): 16 bits in all while the
-// chunks allow it (two radix passes), never fewer than 10 hash bits
-__global__ void mask_keys_kernel(const int32_t* __restrict__ map, int64_t n, int K, int chunk_log, int hb,
-                                 uint32_t* __restrict__ keys, int* __restrict__ flag) {
+// key = 16-bit hash of the offset mask (two radix passes)
+constexpr int kMaskHashBits = 16;
+__global__ void mask_keys_kernel(const int32_t* __restrict__ map, int64_t n, int K, uint32_t* __restrict__ keys,
+                                 int* __restrict__ flag) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *flag = 1;  // the sort below completes before any GEMM reads it
     for (int64_t o = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; o < n;
          o += static_cast<int64_t>(gridDim.x) * blockDim.x) {
         uint32_t m = 0u;
         for (int k = 0; k < K; ++k) m |= (map[o * K + k] >= 0 ? 1u : 0u) << k;
-        const uint32_t chunk = chunk_log ? static_cast<uint32_t>(o >> chunk_log) : 0u;
-        keys[o] = (chunk << hb) | ((m * 0x9E3779B1u) >> (32 - hb));
+        keys[o] = (m * 0x9E3779B1u) >> (32 - kMaskHashBits);
     }
 }
 
@@ -208,14 +173,10 @@ static void build_order(const int32_t* map, int64_t n, int K, int32_t* order, in
     if (!use_order(n, K)) return;
     uint32_t* kin = scratch.take<uint32_t>(n);
     uint32_t* kout = scratch.take<uint32_t>(n);
-    const int cl = order_chunk_log();
-    const int cb = cl ? prim::bits_needed(static_cast<uint64_t>((n - 1) >> cl)) : 0;
-    const int hb = std::max(10, 16 - cb);
-    mask_keys_kernel<<<stream_grid(n, 256), 256, 0, st>>>(map, n, K, cl, hb, kin, flag);
+    mask_keys_kernel<<<stream_grid(n, 256), 256, 0, st>>>(map, n, K, kin, flag);
     O3DML_LAUNCH_CHECK();
-    const int bits = hb + cb;
-    O3DML_REQUIRE(bits <= 32, "tile order: too many row chunks");
-    prim::radix_sort_pairs<uint32_t>(kin, nullptr, kout, reinterpret_cast<uint32_t*>(order), n, bits, scratch, st);
+    prim::radix_sort_pairs<uint32_t>(kin, nullptr, kout, reinterpret_cast<uint32_t*>(order), n, kMaskHashBits, scratch,
+                                     st);
     if (use_tile_map()) {
         tile_map_kernel<<<stream_grid(tile_map_entries(n, K), 256), 256, 0, st>>>(map, order, n, K, tmap);
         O3DML_LAUNCH_CHECK();
@@ -238,8 +199,9 @@ __global__ void transpose_filters_kernel(const float* __restrict__ w, int K, int
 // implicit GEMM (forward / dIn): one wave owns 32 output rows x 32 output
 // channels and walks the (offset, Cin-chunk) stages its rows use.  Operands go
 // straight from global memory into registers in the MFMA layout — lane (i, h)
-// gathers 16 consecutive channels [c0 + 16h, +16) of row i's input (4 x 16-B
-// loads) and the matching 16 weights of column i — so no LDS and no barriers;
+// gathers 16 consecutive channels [c0 + 16h, +16) of row i's input (single
+// words: this kernel takes the shapes with cin % 4 != 0 or unaligned operands)
+// and the matching 16 weights of column i — so no LDS and no barriers;
 // the next stage's loads are issued before the current stage's 16
 // v_mfma_f32_32x32x2_f32 (reduction index permuted consistently on A and B:
 // step s pairs channels c0+s and c0+16+s), hiding the gather latency.
@@ -287,7 +249,6 @@ __device__ __forceinline__ float pre_act(float v, float s, float b) { return fma
 __device__ __attribute__((aligned(16))) float g_zero_page[16];
 __device__ float g_one_page[1] = {1.f};
 
-template <bool VEC4>
 __device__ __forceinline__ void gemm_load(GemmStage& st, int32_t m, int K, int64_t o, int k, int c0, int h, int col,
                                           const float* __restrict__ src, const float* __restrict__ sscale,
                                           const float* __restrict__ pscale, const float* __restrict__ Wt, int cin,
@@ -301,38 +262,14 @@ __device__ __forceinline__ void gemm_load(GemmStage& st, int32_t m, int K, int64
     st.s2 = *(pscale ? pscale + (valid ? o : 0) * K + k : g_one_page);
     st.v = valid ? 1.f : 0.f;
     const float* row = src + mr * cin;
-    if (VEC4) {  // cin % 4 == 0: float4 granules
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = cb + 4 * q;
-            const float4 v = *reinterpret_cast<const float4*>((valid && c < cin) ? row + c : g_zero_page);
-            st.a[4 * q] = v.x;
-            st.a[4 * q + 1] = v.y;
-            st.a[4 * q + 2] = v.z;
-            st.a[4 * q + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) st.a[s] = *((valid && cb + s < cin) ? row + cb + s : g_zero_page);
-    }
+    for (int s = 0; s < 16; ++s) st.a[s] = *((valid && cb + s < cin) ? row + cb + s : g_zero_page);
     // B from the transposed filters Wt[k][col][c]: column col's 16 weights are
-    // contiguous, so the same four 16-B loads as the A side
+    // contiguous, as the A side
     const bool colv = live && col < cout;  // a dead stage reads only the zero page
     const float* wr = Wt + (static_cast<int64_t>(k) * cout + (colv ? col : 0)) * cin;
-    if (VEC4) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = cb + 4 * q;
-            const float4 v = *reinterpret_cast<const float4*>((colv && c < cin) ? wr + c : g_zero_page);
-            st.b[4 * q] = v.x;
-            st.b[4 * q + 1] = v.y;
-            st.b[4 * q + 2] = v.z;
-            st.b[4 * q + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) st.b[s] = *((colv && cb + s < cin) ? wr + cb + s : g_zero_page);
-    }
+    for (int s = 0; s < 16; ++s) st.b[s] = *((colv && cb + s < cin) ? wr + cb + s : g_zero_page);
 }
 
 // Split s of nsplit owns the global stages (offset k, chunk c), g = k*nch + c,
@@ -359,53 +296,17 @@ __device__ __forceinline__ void gemm_finish(GemmStage& st, int c0, int h, const 
     for (int s = 0; s < 16; ++s) st.a[s] = (PRE ? pre_act(st.a[s], lps[cb + s], lpb[cb + s]) : st.a[s]) * sc;
 }
 
-// Split-K store: the wave writes its raw 32 x 32 partial tile into slab s;
-// with tile counters (counters.hpp) the LAST of the nsplit waves owning the
-// tile then sums the slabs in split order and applies split_reduce_kernel's
-// epilogue (same arithmetic, same bits) — no reduce launch.  orow32: the 32
-// output rows of the tile (-1 = none).
-__device__ __forceinline__ void split_store_finish(const f32x16& acc, const int32_t* orow32, int h, int col,
-                                                   int lane, int s, int nsplit, int64_t n_out, int cout,
-                                                   float* __restrict__ part, uint32_t* __restrict__ counters,
-                                                   int64_t tile, const float* __restrict__ oscale,
-                                                   const float* __restrict__ bias,
-                                                   const float* __restrict__ residual, float* __restrict__ out) {
-    const int64_t total = n_out * cout;
-    float* P = part + static_cast<int64_t>(s) * total;
+// Split-K store: the wave writes its raw 32 x 32 partial tile into slab s
+// (split_reduce_kernel sums the slabs and applies the epilogue).  orow32: the
+// 32 output rows of the tile (-1 = none).
+__device__ __forceinline__ void split_store(const f32x16& acc, const int32_t* orow32, int h, int col, int s,
+                                            int64_t n_out, int cout, float* __restrict__ part) {
+    float* P = part + static_cast<int64_t>(s) * n_out * cout;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int64_t orr = orow32[(r & 3) + 8 * (r >> 2) + 4 * h];
-        if (orr >= 0 && col < cout) {
-            if (counters)  // agent-scope store: written through to the device-coherent level
-                __hip_atomic_store(P + orr * cout + col, acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else
-                P[orr * cout + col] = acc[r];
-        }
+        if (orr >= 0 && col < cout) P[orr * cout + col] = acc[r];
     }
-    if (!counters) return;  // split_reduce_kernel finishes
-    // arrival once the slab stores are complete (no device-scope fence: on the
-    // 8-XCD part it writes back the whole L2 per wave); the last wave reads
-    // the slabs with agent-scope loads
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint32_t prev = 0;
-    if (lane == 0) prev = atomicAdd(counters + tile, 1u);
-    prev = __builtin_amdgcn_readfirstlane(prev);
-    if (prev != static_cast<uint32_t>(nsplit - 1)) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int64_t orr = orow32[(r & 3) + 8 * (r >> 2) + 4 * h];
-        if (orr >= 0 && col < cout) {
-            const int64_t e = orr * cout + col;
-            float v = 0.f;
-            for (int sp = 0; sp < nsplit; ++sp)
-                v += __hip_atomic_load(part + sp * total + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (oscale) v *= oscale[orr];
-            if (bias) v += bias[col];
-            if (residual) v += residual[e];
-            out[e] = v;
-        }
-    }
-    if (lane == 0) atomicExch(counters + tile, 0u);  // ready for the next launch
 }
 
 // The map rows of a tile into LDS with every global load in flight at once:
@@ -488,7 +389,7 @@ __device__ __forceinline__ unsigned load_map_tile_direct(const int32_t* __restri
     return map_tile_commit<ROWS, T>(r, K, t, mtile);
 }
 
-template <bool VEC4, bool PRE>
+template <bool PRE>
 __global__ void __launch_bounds__(kGemmThreads)
 implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ order, const int* order_flag,
                      int K, int64_t n_out,
@@ -496,8 +397,7 @@ implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict_
                      const float* __restrict__ sscale, const float* __restrict__ pscale,
                      const float* __restrict__ Wt /*[K][cout][cin]*/, int cin, int cout,
                      const float* __restrict__ oscale, const float* __restrict__ bias, float* __restrict__ out,
-                     int nsplit, float* __restrict__ part, GemmPrologue pre, const float* __restrict__ residual,
-                     uint32_t* __restrict__ counters) {
+                     int nsplit, float* __restrict__ part, GemmPrologue pre, const float* __restrict__ residual) {
     __shared__ float lpre[PRE ? 2 * (kPreMax + 32) : 1];
     float* lps = lpre;
     float* lpb = lpre + (PRE ? kPreMax + 32 : 0);
@@ -562,7 +462,7 @@ implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict_
         };
         GemmStage sa, sb;
         int ka = __builtin_ctz(u), ca = (j0 % nch) * 32, kb = 0, cb = 0;
-        gemm_load<VEC4>(sa, mtile[i * K + ka], K, o, ka, ca, h, col, src, sscale, pscale, Wt, cin, cout);
+        gemm_load(sa, mtile[i * K + ka], K, o, ka, ca, h, col, src, sscale, pscale, Wt, cin, cout);
         for (int j = j0;; j += 2) {
             kb = ka;
             cb = ca;
@@ -571,7 +471,7 @@ implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict_
             // page): a skipped load on one path makes the compiler's wait counts
             // conservative at the join and the MFMAs would wait for these loads
             const bool lb = j + 1 < j1;
-            gemm_load<VEC4>(sb, lb ? mtile[i * K + kb] : -1, K, o, kb, cb, h, col, src, sscale, pscale, Wt, cin, cout,
+            gemm_load(sb, lb ? mtile[i * K + kb] : -1, K, o, kb, cb, h, col, src, sscale, pscale, Wt, cin, cout,
                             lb);
             __builtin_amdgcn_sched_barrier(0);  // keep the loads ahead of the MFMAs
             gemm_finish<PRE>(sa, ca, h, lps, lpb);
@@ -582,7 +482,7 @@ implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict_
             ca = cb;
             advance(ka, ca);
             const bool la = j + 2 < j1;
-            gemm_load<VEC4>(sa, la ? mtile[i * K + ka] : -1, K, o, ka, ca, h, col, src, sscale, pscale, Wt, cin, cout,
+            gemm_load(sa, la ? mtile[i * K + ka] : -1, K, o, ka, ca, h, col, src, sscale, pscale, Wt, cin, cout,
                             la);
             __builtin_amdgcn_sched_barrier(0);
             gemm_finish<PRE>(sb, cb, h, lps, lpb);
@@ -591,11 +491,8 @@ implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict_
             if (j + 2 >= j1) break;
         }
     }
-    if (nsplit > 1) {  // raw partial sums; the tile's last wave (or split_reduce_kernel) finishes
-        split_store_finish(acc, orow, h, col, lane, s, nsplit, n_out, cout, part, counters,
-                           (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * (kGemmThreads / 64) +
-                                   (threadIdx.x >> 6),
-                           oscale, bias, residual, out);
+    if (nsplit > 1) {  // raw partial sums; split_reduce_kernel finishes
+        split_store(acc, orow, h, col, s, n_out, cout, part);
         return;
     }
     // epilogue: C/D map row = (r&3) + 8*(r>>2) + 4*(lane>>5), col = lane&31
@@ -626,9 +523,11 @@ implicit_gemm_kernel(const int32_t* __restrict__ map, const int32_t* __restrict_
 // p ^ (r & 7) — the swizzle sits on the global source address because the
 // DMA's LDS destination is lane-linear — read back in the MFMA layout with
 // ds_read_b128 (lane (i, h): pieces 4h .. 4h+3 of row i), conflict-free over
-// any 8 consecutive rows.  One buffer per operand and wave: stage j is read
-// into registers, then stage j+1's DMA is issued into the same buffer and
-// runs under stage j's 16 MFMAs.
+// any 8 consecutive rows.  The gathered rows (A) go this way; the filters (B,
+// L2-resident) come as fragment-shaped 16-B loads straight into registers, so
+// a wave needs one 4-KiB stage buffer.  Stage j is read into registers, then
+// stage j+1's DMA is issued into the same buffer and runs under stage j's 16
+// MFMAs.
 // --------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
@@ -636,13 +535,11 @@ __device__ __forceinline__ void glds16(const float* g, float* lds_wave_base) {
     __builtin_amdgcn_global_load_lds(g, (lds_void_ptr)(lds_wave_base), 16, 0, 0);
 }
 
-// DMA of one stage (offset k, channels [c0, c0+32)) into abuf / bbuf, plus the
-// row factors of lane (i, h)'s row i into st.
-// BREG: B (the filters, L2-resident) as fragment-shaped 16-B loads straight
-// into st.b instead of through LDS — half the LDS per wave, so more waves.
+// DMA of one stage's rows (offset k, channels [c0, c0+32)) into abuf, plus the
+// filter fragment and the row factors of lane (i, h)'s row i into st.
 // SC: row / pair scales present (importance, normalisation); without them the
 // factors are 1 and no per-stage scale loads are issued
-// BUF (cin % 32 == 0, operands < 2 GiB, no scales, BREG): the rows and the
+// BUF (cin % 32 == 0, operands < 2 GiB, no scales): the rows and the
 // filters through buffer resources with 32-bit offsets — a missing row or
 // column gets an offset past the resource's range, which the buffer unit
 // answers with zeros (no zero-page select, no 64-bit address arithmetic:
@@ -685,9 +582,9 @@ __device__ __forceinline__ StageMap lds_map(const int32_t* mtile, int K, int k, 
     return m;
 }
 
-template <bool BREG, bool SC = true, bool BUF = false, bool BS = false>
-__device__ __forceinline__ void lds_issue_map(float* abuf, float* bbuf, const StageMap& sm, int k, int c0, int lane,
-                                              int64_t o, int i, int col0, const float* __restrict__ src,
+template <bool SC, bool BUF, bool BS>
+__device__ __forceinline__ void lds_issue_map(float* abuf, const StageMap& sm, int k, int c0, int lane, int64_t o,
+                                              int i, int col0, const float* __restrict__ src,
                                               const float* __restrict__ sscale, const float* __restrict__ pscale,
                                               const float* __restrict__ Wt, int K, int cin, int cout, bool live,
                                               GemmStage& st, const GemmRsrc* rs) {
@@ -695,7 +592,7 @@ __device__ __forceinline__ void lds_issue_map(float* abuf, float* bbuf, const St
     const int32_t* mq = sm.mq;
     const int32_t mi = sm.mi;
     if constexpr (BUF) {
-        static_assert(BREG && !SC, "buffer addressing: filters in registers, no scales");
+        static_assert(!SC, "buffer addressing: no scales");
         const uint32_t row_bytes = static_cast<uint32_t>(cin) * 4u;
 #if O3DML_GEMM_DIAG != 2  // cost-split diagnostics: 2 = no row gathers
 #pragma unroll
@@ -753,27 +650,20 @@ __device__ __forceinline__ void lds_issue_map(float* abuf, float* bbuf, const St
         const int32_t m = mq[q];
         const float* ga = (m >= 0 && c < cin) ? src + static_cast<int64_t>(m) * cin + c : g_zero_page;
         glds16(ga, abuf + 256 * q);
-        if constexpr (!BREG) {
-            const int cc = col0 + r;
-            const float* gb = (live && cc < cout && c < cin) ? Wt + (static_cast<int64_t>(k) * cout + cc) * cin + c
-                                                              : g_zero_page;
-            glds16(gb, bbuf + 256 * q);
-        }
     }
-    if constexpr (BREG) {  // lane (i, h): channels [c0 + 16h, +16) of column col0 + i
-        const int cb = c0 + 16 * (lane >> 5);
-        const int col = col0 + i;
-        const bool colv = live && col < cout;
-        const float* wr = Wt + (static_cast<int64_t>(k) * cout + (colv ? col : 0)) * cin;
+    // the filters: lane (i, h) takes channels [c0 + 16h, +16) of column col0 + i
+    const int cb = c0 + 16 * (lane >> 5);
+    const int col = col0 + i;
+    const bool colv = live && col < cout;
+    const float* wr = Wt + (static_cast<int64_t>(k) * cout + (colv ? col : 0)) * cin;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = cb + 4 * q;
-            const float4 v = *reinterpret_cast<const float4*>((colv && c < cin) ? wr + c : g_zero_page);
-            st.b[4 * q] = v.x;
-            st.b[4 * q + 1] = v.y;
-            st.b[4 * q + 2] = v.z;
-            st.b[4 * q + 3] = v.w;
-        }
+    for (int q = 0; q < 4; ++q) {
+        const int c = cb + 4 * q;
+        const float4 v = *reinterpret_cast<const float4*>((colv && c < cin) ? wr + c : g_zero_page);
+        st.b[4 * q] = v.x;
+        st.b[4 * q + 1] = v.y;
+        st.b[4 * q + 2] = v.z;
+        st.b[4 * q + 3] = v.w;
     }
     const bool valid = mi >= 0;
     if constexpr (SC) {
@@ -785,20 +675,8 @@ __device__ __forceinline__ void lds_issue_map(float* abuf, float* bbuf, const St
     st.v = valid ? 1.f : 0.f;
 }
 
-template <bool BREG, bool SC = true, bool BUF = false, bool BS = false>
-__device__ __forceinline__ void lds_issue(float* abuf, float* bbuf, const int32_t* mtile, int K, int k, int c0,
-                                          int lane, int64_t o, int i, int col0, const float* __restrict__ src,
-                                          const float* __restrict__ sscale, const float* __restrict__ pscale,
-                                          const float* __restrict__ Wt, int cin, int cout, bool live, GemmStage& st,
-                                          const GemmRsrc* rs = nullptr) {
-    // all LDS reads of the map first (a DMA in between would order after them)
-    const StageMap sm = lds_map(mtile, K, k, lane, i, live);
-    lds_issue_map<BREG, SC, BUF, BS>(abuf, bbuf, sm, k, c0, lane, o, i, col0, src, sscale, pscale, Wt, K, cin, cout,
-                                     live, st, rs);
-}
-
-template <bool BREG>
-__device__ __forceinline__ void lds_read(const float* abuf, const float* bbuf, int i, int h, GemmStage& st) {
+// the gathered rows of a stage from its LDS image, in the MFMA layout
+__device__ __forceinline__ void lds_read(const float* abuf, int i, int h, GemmStage& st) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int slot = (4 * h + q) ^ (i & 7);
@@ -807,13 +685,6 @@ __device__ __forceinline__ void lds_read(const float* abuf, const float* bbuf, i
         st.a[4 * q + 1] = va.y;
         st.a[4 * q + 2] = va.z;
         st.a[4 * q + 3] = va.w;
-        if constexpr (!BREG) {
-            const float4 vb = *reinterpret_cast<const float4*>(bbuf + 32 * i + 4 * slot);
-            st.b[4 * q] = vb.x;
-            st.b[4 * q + 1] = vb.y;
-            st.b[4 * q + 2] = vb.z;
-            st.b[4 * q + 3] = vb.w;
-        }
     }
 }
 
@@ -832,6 +703,9 @@ __device__ __forceinline__ void lds_read(const float* abuf, const float* bbuf, i
 // Fragment of MFMA t (t = 0, 1) on lane (i, h): element j = stage register
 // 8t + j (channel c0 + 16h + 8t + j in the forward GEMM) — the same map on A
 // (row i) and B (column i), so any consistent permutation of the reduction.
+// B_FIRST: the filter fragment is split before the rows (same terms either
+// way; implicit_gemm_shared_kernel's registers were tuned in that order — rows
+// first costs its prologue bf16x6 form 16 registers, 5 -> 4 waves per SIMD).
 template <int NT>
 __device__ __forceinline__ void split_bf16x8(const float* v, bf16x8& hi, bf16x8& mid, bf16x8& lo) {
 #pragma unroll
@@ -843,13 +717,14 @@ __device__ __forceinline__ void split_bf16x8(const float* v, bf16x8& hi, bf16x8&
     }
 }
 
-template <int NT, class Stage>
+template <int NT, bool B_FIRST, class Stage>
 __device__ __forceinline__ void mfma_stage_split(const Stage& cu, f32x16& acc) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         bf16x8 ah, am, al, bh, bm, bl;
+        if constexpr (B_FIRST) split_bf16x8<NT>(cu.b + 8 * t, bh, bm, bl);
         split_bf16x8<NT>(cu.a + 8 * t, ah, am, al);
-        split_bf16x8<NT>(cu.b + 8 * t, bh, bm, bl);
+        if constexpr (!B_FIRST) split_bf16x8<NT>(cu.b + 8 * t, bh, bm, bl);
         if constexpr (NT == 6) {  // smallest terms first
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
@@ -897,13 +772,13 @@ __global__ void split_filters_kernel(const float* __restrict__ wt, int64_t nblk,
 }
 
 // product precision of a GEMM instantiation: 0 = exact f32 MFMA, 3 / 6 = bf16 split
-template <int NT, class Stage>
+template <int NT, bool B_FIRST = false, class Stage>
 __device__ __forceinline__ void mfma_stage(const Stage& cu, f32x16& acc) {
     if constexpr (NT == 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(cu.a[r], cu.b[r], acc, 0, 0, 0);
     } else {
-        mfma_stage_split<NT>(cu, acc);
+        mfma_stage_split<NT, B_FIRST>(cu, acc);
     }
 }
 
@@ -930,11 +805,9 @@ __device__ uint64_t g_gemm_trace[kTraceWaves * kTraceSlots];
 #define O3DML_TRACE(slot) do {} while (0)
 #endif
 
-// DEPTH 2 (BUF only, O3DML_GEMM_DEPTH=2): two stages in flight per wave —
-// stage j+2's DMA is issued while stage j is multiplied.  Off by default:
-// 12 instead of 16 waves per CU (136 registers, 49 KiB LDS per workgroup), and
-// same-session A/B 3-8 % slower at 32->32 / 64->32 (tools/gemm_probe.py)
-template <bool PRE, bool BREG, int NT = 0, bool SC = true, bool BUF = false, int DEPTH = 1, bool BS = false>
+// PRE: eval prologue; NT: product precision (mfma_stage); SC, BUF: see
+// lds_issue_map; BS: filters split once per call (NT 6 on the buffer path)
+template <bool PRE, int NT, bool SC, bool BUF = false, bool BS = false>
 __global__ void __launch_bounds__(kGemmThreads)
 implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ order,
                          const int* order_flag, int K, int64_t n_out,
@@ -942,9 +815,10 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
                          const float* __restrict__ pscale, const float* __restrict__ Wt /*[K][cout][cin]*/, int cin,
                          int cout, const float* __restrict__ oscale, const float* __restrict__ bias,
                          float* __restrict__ out, int nsplit, float* __restrict__ part, GemmPrologue pre,
-                         const float* __restrict__ residual, uint32_t* __restrict__ counters) {
+                         const float* __restrict__ residual) {
+    static_assert(!BS || (BUF && NT == 6), "split filters: bf16x6 buffer path");
     __shared__ float lpre[PRE ? 2 * (kPreMax + 32) : 1];
-    __shared__ __attribute__((aligned(16))) float stage_all[kGemmThreads / 64][BREG && DEPTH == 1 ? 1 : 2][32 * 32];
+    __shared__ __attribute__((aligned(16))) float stage_all[kGemmThreads / 64][32 * 32];
     __shared__ int32_t mtile_all[kGemmThreads / 64][32 * 32];
     __shared__ int32_t orow_all[kGemmThreads / 64][32];
 #if O3DML_GEMM_TRACE
@@ -962,8 +836,7 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: item decode in scalars
     int32_t* mtile = mtile_all[w];
     int32_t* orow = orow_all[w];
-    float* abuf = stage_all[w][0];
-    float* bbuf = stage_all[w][BREG ? 0 : 1];  // unused with BREG
+    float* abuf = stage_all[w];
     // Work items (32-row tile, column block, split).  Default: one wave per
     // item, the grid's (x, y, z).  Persistent grid (pre.pcols > 0): only as
     // many waves as are resident, each looping over items tile-major, so no
@@ -984,7 +857,7 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
     int32_t nrow = -1;
     bool have_next = false;
     if (order && pre.tmap && it0 < n_items) {
-        const int64_t tw0 = pers ? it0 / per_tile : xcd_block() * (kGemmThreads / 64) + w;
+        const int64_t tw0 = pers ? it0 / per_tile : static_cast<int64_t>(blockIdx.x) * (kGemmThreads / 64) + w;
         const int64_t f0 = tw0 * 32;
         if (f0 < n_out) {
             const int ln = threadIdx.x & 63;
@@ -1014,10 +887,7 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
         cy = r % pre.pcols;
         s = r / pre.pcols;
     } else {
-        // XCD-contiguous tiles (grid a multiple of 8): XCD x takes one
-        // contiguous eighth of the (spatially chunked) tile order, so its L2
-        // holds the input rows that eighth gathers
-        tw = xcd_block() * (kGemmThreads / 64) + w;
+        tw = static_cast<int64_t>(blockIdx.x) * (kGemmThreads / 64) + w;
         cy = blockIdx.y;
         s = blockIdx.z;
     }
@@ -1092,81 +962,18 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
         nrow = lane < 32 && no0 + lane < n_out ? order[no0 + lane] : -1;
         have_next = true;
     }
-    if (DEPTH == 2 && j0 < j1) {
-        static_assert(DEPTH == 1 || (BUF && BREG && !SC), "two stages in flight: buffer path only");
-        unsigned u = used;
-        for (int t = j0 / nch; t > 0; --t) u &= u - 1u;
-        int k = __builtin_ctz(u), c0 = (j0 % nch) * 32;
-        auto advance = [&]() {
-            c0 += 32;
-            if (c0 >= cin) {
-                c0 = 0;
-                u &= u - 1u;
-                k = u ? __builtin_ctz(u) : 0;
-            }
-        };
-        const GemmRsrc rs = gemm_rsrc(src, Wt, pre);
-        float* buf1 = stage_all[w][1];
-        GemmStage s0, s1, cu;
-        int c00 = c0;
-        lds_issue<true, false, true>(abuf, nullptr, mtile, K, k, c0, lane, o, i, col0, src, sscale, pscale, Wt, cin,
-                                     cout, true, s0, &rs);
-        advance();
-        int c01 = c0;
-        lds_issue<true, false, true>(buf1, nullptr, mtile, K, k, c0, lane, o, i, col0, src, sscale, pscale, Wt, cin,
-                                     cout, j0 + 1 < j1, s1, &rs);
-        advance();
-        // every stage issues exactly 8 vector-memory ops (4 row DMAs, 4 filter
-        // loads; dead stages read zeros), so vmcnt(8) = the older stage landed
-        for (int j = j0; j < j1; j += 2) {
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            lds_read<true>(abuf, nullptr, i, h, cu);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) cu.b[r] = s0.b[r];
-            cu.s1 = s0.s1;
-            cu.s2 = s0.s2;
-            cu.v = s0.v;  // the prologue zeroes a missing row (relu(0 * s + b) != 0)
-            int cj = c00;
-            c00 = c0;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lds_issue<true, false, true>(abuf, nullptr, mtile, K, k, c0, lane, o, i, col0, src, sscale, pscale, Wt,
-                                         cin, cout, j + 2 < j1, s0, &rs);
-            advance();
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_finish<PRE, false>(cu, cj, h, lps, lpb);
-            mfma_stage<NT>(cu, acc);
-            if (j + 1 >= j1) break;
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            lds_read<true>(buf1, nullptr, i, h, cu);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) cu.b[r] = s1.b[r];
-            cu.s1 = s1.s1;
-            cu.s2 = s1.s2;
-            cu.v = s1.v;  // the prologue zeroes a missing row (relu(0 * s + b) != 0)
-            cj = c01;
-            c01 = c0;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lds_issue<true, false, true>(buf1, nullptr, mtile, K, k, c0, lane, o, i, col0, src, sscale, pscale, Wt,
-                                         cin, cout, j + 3 < j1, s1, &rs);
-            advance();
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_finish<PRE, false>(cu, cj, h, lps, lpb);
-            mfma_stage<NT>(cu, acc);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dead DMAs have landed before the wave exits
-    } else if (j0 < j1) {
-        static_assert(!BS || (BUF && BREG && !SC && NT == 6 && DEPTH == 1), "split filters: bf16x6 buffer path");
+    if (j0 < j1) {
         unsigned u = used;
         for (int t = j0 / nch; t > 0; --t) u &= u - 1u;
         int k = __builtin_ctz(u), c0 = (j0 % nch) * 32;
         GemmStage nx, cu;
         const GemmRsrc rs = gemm_rsrc(src, Wt, pre);
-        lds_issue<BREG, SC, BUF, BS>(abuf, bbuf, mtile, K, k, c0, lane, o, i, col0, src, sscale, pscale, Wt, cin,
-                                     cout, true, nx, &rs);
+        lds_issue_map<SC, BUF, BS>(abuf, lds_map(mtile, K, k, lane, i, true), k, c0, lane, o, i, col0, src, sscale,
+                                   pscale, Wt, K, cin, cout, true, nx, &rs);
         for (int j = j0; j < j1; ++j) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stage j in LDS, its row factors in nx
             if (j - j0 < 8) O3DML_TRACE(4 + j - j0);
-            const int kj = k, cj = c0;
+            const int cj = c0;
             c0 += 32;
             if (c0 >= cin) {
                 c0 = 0;
@@ -1176,12 +983,12 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
             // the next stage's map entries are read beside this stage's rows
             // (different LDS arrays), so one LDS wait covers both
             const StageMap sm = lds_map(mtile, K, k, lane, i, j + 1 < j1);
-            lds_read<BREG>(abuf, bbuf, i, h, cu);
+            lds_read(abuf, i, h, cu);
             __builtin_amdgcn_sched_barrier(0);  // both read groups issued before any waits on them
             if constexpr (BS) {
 #pragma unroll
                 for (int m = 0; m < 6; ++m) cu.bs[m] = nx.bs[m];
-            } else if constexpr (BREG) {
+            } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) cu.b[r] = nx.b[r];
             }
@@ -1189,10 +996,9 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
             cu.s2 = nx.s2;
             cu.v = nx.v;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // buffer read out before the next DMA
-            lds_issue_map<BREG, SC, BUF, BS>(abuf, bbuf, sm, k, c0, lane, o, i, col0, src, sscale, pscale, Wt, K, cin,
-                                             cout, j + 1 < j1, nx, &rs);
+            lds_issue_map<SC, BUF, BS>(abuf, sm, k, c0, lane, o, i, col0, src, sscale, pscale, Wt, K, cin, cout,
+                                       j + 1 < j1, nx, &rs);
             __builtin_amdgcn_sched_barrier(0);
-            (void)kj;
             gemm_finish<PRE, SC>(cu, cj, h, lps, lpb);
             if constexpr (BS) mfma_stage_bs(cu, acc);
             else mfma_stage<NT>(cu, acc);
@@ -1201,10 +1007,7 @@ implicit_gemm_lds_kernel(const int32_t* __restrict__ map, const int32_t* __restr
     }
     O3DML_TRACE(12);
     if (nsplit > 1) {
-        split_store_finish(acc, orow, h, col, lane, s, nsplit, n_out, cout, part, counters,
-                           pers ? cy * ntw + tw
-                                : (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * (kGemmThreads / 64) + w,
-                           oscale, bias, residual, out);
+        split_store(acc, orow, h, col, s, n_out, cout, part);
         O3DML_TRACE(13);
         continue;
     }
@@ -1249,29 +1052,16 @@ O3DML_API int o3dml_gemm_trace_clear() {
 // output are those of implicit_gemm_lds_kernel (same sums).
 // --------------------------------------------------------------------------
 // DMA of this wave's share of one stage: row groups q = w, w + NW, ... of the
-// tile's 4*RB groups of 8 rows (lane-linear LDS destination, swizzled source
-// as in lds_issue)
-template <int NW, int RB, bool BUF = false>
+// tile's 4 groups of 8 rows (lane-linear LDS destination, swizzled source as
+// in lds_issue_map)
+template <int NW>
 __device__ __forceinline__ void shared_issue(float* abuf, const int32_t* mtile, int K, int k, int c0, int lane, int w,
-                                             const float* __restrict__ src, int cin, bool live,
-                                             const GemmRsrc* rs = nullptr) {
-    constexpr int NQ = 4 * RB / NW;
+                                             const float* __restrict__ src, int cin, bool live) {
+    constexpr int NQ = 4 / NW;
     const int sl = lane & 7;
     int32_t mq[NQ];
 #pragma unroll
     for (int t = 0; t < NQ; ++t) mq[t] = live ? mtile[(8 * (w + NW * t) + (lane >> 3)) * K + k] : -1;
-    if constexpr (BUF) {  // buffer addressing as lds_issue (cin % 32 == 0)
-        const uint32_t row_bytes = static_cast<uint32_t>(cin) * 4u;
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            const int q = w + NW * t;
-            const int r = 8 * q + (lane >> 3);
-            const uint32_t cb = static_cast<uint32_t>(c0 + 4 * (sl ^ (r & 7))) * 4u;
-            const uint32_t off = mq[t] >= 0 ? static_cast<uint32_t>(mq[t]) * row_bytes + cb : kNoRow;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs->src, (lds_void_ptr)(abuf + 256 * q), 16, off, 0, 0, 0);
-        }
-        return;
-    }
 #pragma unroll
     for (int t = 0; t < NQ; ++t) {
         const int q = w + NW * t;
@@ -1282,40 +1072,15 @@ __device__ __forceinline__ void shared_issue(float* abuf, const int32_t* mtile, 
     }
 }
 
-template <int RB>
-struct SharedStage {
-    float a[RB][16], b[16];
-    float sc[RB];  // row factor (importance x pair scale, 0 for a missing row)
-};
-
-template <int RB, bool SC = true, bool BUF = false>
-__device__ __forceinline__ void shared_regs(const int32_t* mtile, int K, int k, int c0, int lane, const int64_t* o,
-                                            int i, int col, const float* __restrict__ sscale,
+// the wave's filter fragment of one stage (column col) and the row factors of
+// lane (i, h)'s row i into st
+template <bool SC>
+__device__ __forceinline__ void shared_regs(const int32_t* mtile, int K, int k, int c0, int lane, int64_t o, int i,
+                                            int col, const float* __restrict__ sscale,
                                             const float* __restrict__ pscale, const float* __restrict__ Wt, int cin,
-                                            int cout, bool live, SharedStage<RB>& st, float (&s1)[RB],
-                                            float (&s2)[RB], bool (&v)[RB], const GemmRsrc* rs = nullptr) {
+                                            int cout, bool live, GemmStage& st) {
     const int cb = c0 + 16 * (lane >> 5);
     const bool colv = live && col < cout;
-    if constexpr (BUF) {
-        static_assert(!SC, "buffer addressing: no scales");
-        const uint32_t boff =
-                colv ? (static_cast<uint32_t>(k * cout + col) * static_cast<uint32_t>(cin) + static_cast<uint32_t>(cb)) * 4u
-                     : kNoRow;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 x = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs->w, boff + 16u * q, 0, 0));
-            st.b[4 * q] = x.x;
-            st.b[4 * q + 1] = x.y;
-            st.b[4 * q + 2] = x.z;
-            st.b[4 * q + 3] = x.w;
-        }
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            v[rb] = live && mtile[(32 * rb + i) * K + k] >= 0;
-            s1[rb] = s2[rb] = 1.f;
-        }
-        return;
-    }
     const float* wr = Wt + (static_cast<int64_t>(k) * cout + (colv ? col : 0)) * cin;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1326,56 +1091,19 @@ __device__ __forceinline__ void shared_regs(const int32_t* mtile, int K, int k, 
         st.b[4 * q + 2] = x.z;
         st.b[4 * q + 3] = x.w;
     }
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        const int32_t mi = live ? mtile[(32 * rb + i) * K + k] : -1;
-        v[rb] = mi >= 0;
-        if constexpr (SC) {
-            s1[rb] = *(sscale ? sscale + (v[rb] ? mi : 0) : g_one_page);
-            s2[rb] = *(pscale ? pscale + (v[rb] ? o[rb] : 0) * K + k : g_one_page);
-        } else {
-            s1[rb] = s2[rb] = 1.f;
-        }
-    }
-}
-
-// RB row blocks against one column block: B split once, each row block's A
-// split and multiplied into its accumulator (same per-output sums as
-// mfma_stage: the reduction order of one accumulator does not change)
-template <int NT, int RB>
-__device__ __forceinline__ void mfma_stage_rb(const SharedStage<RB>& cu, f32x16 (&acc)[RB]) {
-    if constexpr (NT == 0) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(cu.a[rb][r], cu.b[r], acc[rb], 0, 0, 0);
+    const int32_t mi = live ? mtile[i * K + k] : -1;
+    const bool valid = mi >= 0;
+    if constexpr (SC) {
+        st.s1 = *(sscale ? sscale + (valid ? mi : 0) : g_one_page);
+        st.s2 = *(pscale ? pscale + (valid ? o : 0) * K + k : g_one_page);
     } else {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            bf16x8 bh, bm, bl;
-            split_bf16x8<NT>(cu.b + 8 * t, bh, bm, bl);
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                bf16x8 ah, am, al;
-                split_bf16x8<NT>(cu.a[rb] + 8 * t, ah, am, al);
-                if constexpr (NT == 6) {
-                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[rb], 0, 0, 0);
-                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[rb], 0, 0, 0);
-                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[rb], 0, 0, 0);
-                }
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[rb], 0, 0, 0);
-            }
-        }
+        st.s1 = st.s2 = 1.f;
     }
+    st.v = valid ? 1.f : 0.f;
 }
 
-// The tile: 32*RB output rows (RB row blocks) x NW column blocks; wave w owns
-// column block w for all RB row blocks, so each stage's B fragment (the
-// filters, read by every wave of every tile) feeds RB accumulators.
-template <bool PRE, int NT, int NW, int RB, bool SC = true, bool BUF = false>
+// The tile: 32 output rows x NW column blocks; wave w owns column block w.
+template <bool PRE, int NT, int NW, bool SC>
 __global__ void __launch_bounds__(NW * 64)
 implicit_gemm_shared_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ order,
                             const int* order_flag, int K, int64_t n_out,
@@ -1383,13 +1111,12 @@ implicit_gemm_shared_kernel(const int32_t* __restrict__ map, const int32_t* __re
                             const float* __restrict__ pscale, const float* __restrict__ Wt /*[K][cout][cin]*/,
                             int cin, int cout, const float* __restrict__ oscale, const float* __restrict__ bias,
                             float* __restrict__ out, int nsplit, float* __restrict__ part, GemmPrologue pre,
-                            const float* __restrict__ residual, uint32_t* __restrict__ counters) {
-    constexpr int R = 32 * RB;
+                            const float* __restrict__ residual) {
     __shared__ float lpre[PRE ? 2 * (kPreMax + 32) : 1];
-    __shared__ __attribute__((aligned(16))) float abuf[2][R * 32];
-    __shared__ int32_t mtile[R * 32];
-    __shared__ int32_t orow[R];
-    const int64_t o0 = xcd_block() * R;  // XCD-contiguous tiles, as implicit_gemm_lds_kernel
+    __shared__ __attribute__((aligned(16))) float abuf[2][32 * 32];
+    __shared__ int32_t mtile[32 * 32];
+    __shared__ int32_t orow[32];
+    const int64_t o0 = static_cast<int64_t>(blockIdx.x) * 32;
     if (o0 >= n_out) return;  // whole workgroup, before any barrier
     float* lps = lpre;
     float* lpb = lpre + (PRE ? kPreMax + 32 : 0);
@@ -1407,40 +1134,33 @@ implicit_gemm_shared_kernel(const int32_t* __restrict__ map, const int32_t* __re
     unsigned used = 0u;  // identical in every wave (same rows)
     if (order && pre.tmap) {  // tile order with its map copy: map rows and output rows loaded together
         __shared__ unsigned used_w[NW];
-        for (int t = threadIdx.x; t < R; t += NW * 64) {
-            const int64_t oo = o0 + t;
-            orow[t] = oo < n_out ? order[oo] : -1;
+        if (threadIdx.x < 32) {
+            const int64_t oo = o0 + threadIdx.x;
+            orow[threadIdx.x] = oo < n_out ? order[oo] : -1;
         }
-        const unsigned mw = load_map_tile_direct<R, NW * 64>(pre.tmap + o0 * K, K, threadIdx.x, mtile);
+        const unsigned mw = load_map_tile_direct<32, NW * 64>(pre.tmap + o0 * K, K, threadIdx.x, mtile);
         if (lane == 0) used_w[w] = mw;
         __syncthreads();
 #pragma unroll
         for (int v = 0; v < NW; ++v) used |= used_w[v];
     } else {
-        for (int t = threadIdx.x; t < R; t += NW * 64) {
-            const int64_t oo = o0 + t;
-            orow[t] = oo < n_out ? (order ? order[oo] : static_cast<int32_t>(oo)) : -1;
+        if (threadIdx.x < 32) {
+            const int64_t oo = o0 + threadIdx.x;
+            orow[threadIdx.x] = oo < n_out ? (order ? order[oo] : static_cast<int32_t>(oo)) : -1;
         }
         __syncthreads();
-        load_map_tile<R, NW * 64>(map, orow, K, threadIdx.x, mtile);
+        load_map_tile<32, NW * 64>(map, orow, K, threadIdx.x, mtile);
         __syncthreads();
         for (int k = h; k < K; k += 2) {
-            bool any = false;
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) any |= mtile[(32 * rb + i) * K + k] >= 0;
-            const uint64_t b = __ballot(any);
+            const uint64_t b = __ballot(mtile[i * K + k] >= 0);
             used |= ((h ? (b >> 32) : (b & 0xffffffffull)) != 0ull) ? (1u << k) : 0u;
         }
     }
     used = __builtin_amdgcn_readlane(used, 32) | __builtin_amdgcn_readlane(used, 0);
-    int64_t o[RB];
+    const int64_t o = orow[i] >= 0 ? orow[i] : 0;
+    f32x16 acc;
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) o[rb] = orow[32 * rb + i] >= 0 ? orow[32 * rb + i] : 0;
-    f32x16 acc[RB];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const int nch = (cin + 31) >> 5;
     const int s = blockIdx.z;
     const int j0 = split_stage(used, nch, K, s, nsplit);
@@ -1449,25 +1169,15 @@ implicit_gemm_shared_kernel(const int32_t* __restrict__ map, const int32_t* __re
         unsigned u = used;
         for (int t = j0 / nch; t > 0; --t) u &= u - 1u;
         int k = __builtin_ctz(u), c0 = (j0 % nch) * 32;
-        SharedStage<RB> nx, cu;
-        float s1[RB], s2[RB];
-        bool vv[RB];
-        const GemmRsrc rs = gemm_rsrc(src, Wt, pre);
-        shared_issue<NW, RB, BUF>(abuf[0], mtile, K, k, c0, lane, w, src, cin, true, &rs);
-        shared_regs<RB, SC, BUF>(mtile, K, k, c0, lane, o, i, col, sscale, pscale, Wt, cin, cout, true, nx, s1, s2, vv,
-                                 &rs);
+        GemmStage nx, cu;
+        shared_issue<NW>(abuf[0], mtile, K, k, c0, lane, w, src, cin, true);
+        shared_regs<SC>(mtile, K, k, c0, lane, o, i, col, sscale, pscale, Wt, cin, cout, true, nx);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         for (int j = j0; j < j1; ++j) {
             const int b = (j - j0) & 1;
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                GemmStage ta;
-                lds_read<true>(abuf[b] + 32 * 32 * rb, nullptr, i, h, ta);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) cu.a[rb][r] = ta.a[r];
-                cu.sc[rb] = vv[rb] ? s1[rb] * s2[rb] : 0.f;
-            }
+            lds_read(abuf[b], i, h, cu);
+            const float sc = nx.v != 0.f ? nx.s1 * nx.s2 : 0.f;  // gemm_finish's row factor, taken before nx is reloaded
 #pragma unroll
             for (int r = 0; r < 16; ++r) cu.b[r] = nx.b[r];
             const int cj = c0;
@@ -1479,20 +1189,16 @@ implicit_gemm_shared_kernel(const int32_t* __restrict__ map, const int32_t* __re
             }
             const bool live = j + 1 < j1;
             // the other buffer was last read in stage j-1, before that stage's barrier
-            shared_issue<NW, RB, BUF>(abuf[b ^ 1], mtile, K, k, c0, lane, w, src, cin, live, &rs);
-            shared_regs<RB, SC, BUF>(mtile, K, k, c0, lane, o, i, col, sscale, pscale, Wt, cin, cout, live, nx, s1, s2,
-                                     vv, &rs);
+            shared_issue<NW>(abuf[b ^ 1], mtile, K, k, c0, lane, w, src, cin, live);
+            shared_regs<SC>(mtile, K, k, c0, lane, o, i, col, sscale, pscale, Wt, cin, cout, live, nx);
             __builtin_amdgcn_sched_barrier(0);
             const int cbb = cj + 16 * h;
             if constexpr (PRE || SC) {  // without both the factor is 1 and missing rows are zero already
 #pragma unroll
-                for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        cu.a[rb][r] =
-                                (PRE ? pre_act(cu.a[rb][r], lps[cbb + r], lpb[cbb + r]) : cu.a[rb][r]) * cu.sc[rb];
+                for (int r = 0; r < 16; ++r)
+                    cu.a[r] = (PRE ? pre_act(cu.a[r], lps[cbb + r], lpb[cbb + r]) : cu.a[r]) * sc;
             }
-            mfma_stage_rb<NT, RB>(cu, acc);
+            mfma_stage<NT, true>(cu, acc);
             // the MFMAs stay above the wait: left to the scheduler, all but one
             // sank below it, so stage j+1's loads were waited on before stage j
             // multiplied (no overlap of the gather latency with the MFMAs)
@@ -1501,230 +1207,19 @@ implicit_gemm_shared_kernel(const int32_t* __restrict__ map, const int32_t* __re
             __syncthreads();  // every share landed; stage j's buffer free
         }
     }
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        if (nsplit > 1) {
-            split_store_finish(acc[rb], orow + 32 * rb, h, col, lane, s, nsplit, n_out, cout, part, counters,
-                               ((static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * NW + w) * RB + rb,
-                               oscale, bias, residual, out);
-            continue;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t orr = orow[32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h];
-            if (orr >= 0 && col < cout) {
-                float v = acc[rb][r];
-                if (oscale) v *= oscale[orr];
-                if (bias) v += bias[col];
-                if (residual) v += residual[orr * cout + col];
-                out[orr * cout + col] = v;
-            }
-        }
-    }
-}
-
-// --------------------------------------------------------------------------
-// implicit GEMM on presplit operands (bf16x6 / bf16x3, the default product
-// precision): the hi / mid / lo split of every operand element is done ONCE
-// per call by presplit_kernel — per input row (with the eval prologue and the
-// row importance folded in, as gemm_finish applies them) and per filter
-// element — instead of once per (row, column block, stage) inside the GEMM:
-// the split kernels above spend ~11 VALU instructions per MFMA on it (VALU-
-// bound: 21.8 VALU per MFMA measured with addressing), here the stage loop is
-// DMA + ds_read + MFMA only.  The planes hold exactly the values
-// split_bf16x8 produces in the other kernels and the MFMAs run in the same
-// order, so the sums are bit-identical to implicit_gemm_lds/shared_kernel.
-// Needs cin % 8 == 0 (16-B pieces of 8 bf16) and no per-pair scale (pscale:
-// neighbour importance, which cannot be folded per row).
-//
-// Tile: 32 output rows x NW column blocks (wave w: block w).  A per plane:
-// LDS image [32 rows][4 pieces of 16 B], piece p of row r in slot
-// p ^ ((r >> 2) & 3) (lane (i, h) reads pieces 2h, 2h + 1 of row i: 16
-// consecutive lanes hit 16 distinct 4-bank groups), filled with
-// global_load_lds_dwordx4 (16 rows per instruction, the NP planes x 2 halves
-// dealt over the NW waves); double-buffered when NW > 1 (a barrier per stage
-// publishes it), single-buffered for one wave.  B fragments come straight
-// from the filter planes into registers (L2-resident).
-// --------------------------------------------------------------------------
-template <int NT>
-__global__ void __launch_bounds__(256) presplit_kernel(const float* __restrict__ x, int64_t n, int cin,
-                                                       const float* __restrict__ ps, const float* __restrict__ pb,
-                                                       const float* __restrict__ rscale, bf16x8* __restrict__ hi,
-                                                       bf16x8* __restrict__ mid, bf16x8* __restrict__ lo) {
-    const int g8 = cin >> 3;
-    const int64_t total = n * g8;
-    for (int64_t e = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        const int64_t r = e / g8;
-        const int c = static_cast<int>(e - r * g8) * 8;
-        const float4 v0 = *reinterpret_cast<const float4*>(x + r * cin + c);
-        const float4 v1 = *reinterpret_cast<const float4*>(x + r * cin + c + 4);
-        float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        const float sc = rscale ? rscale[r] : 1.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (ps ? pre_act(v[j], ps[c + j], pb[c + j]) : v[j]) * sc;
-        bf16x8 h, m, l;
-        split_bf16x8<NT>(v, h, m, l);
-        hi[e] = h;
-        mid[e] = m;
-        if constexpr (NT == 6) lo[e] = l;
-    }
-}
-
-template <int NT, int NW, int RB>
-__global__ void __launch_bounds__(NW * 64)
-implicit_gemm_split_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ order, const int* order_flag,
-                           int K, int64_t n_out, const __bf16* __restrict__ ap, int64_t plane_a,
-                           const __bf16* __restrict__ bp /*[plane][K][cout][cin]*/, int64_t plane_b, int cin,
-                           int cout, const float* __restrict__ oscale, const float* __restrict__ bias,
-                           float* __restrict__ out, int nsplit, float* __restrict__ part,
-                           const float* __restrict__ residual, uint32_t* __restrict__ counters) {
-    constexpr int NP = NT == 6 ? 3 : 2;  // planes: hi, mid (, lo)
-    constexpr int NB = NW == 1 ? 1 : 2;  // A image buffers
-    constexpr int R = 32 * RB;           // output rows per tile
-    constexpr int NI = 2 * NP * RB;      // DMA instructions per stage (16 rows of one plane each)
-    __shared__ __attribute__((aligned(16))) __bf16 abuf[NB][RB][NP][32 * 32];
-    __shared__ int32_t mtile[R * 32];
-    __shared__ int32_t orow[R];
-    const int64_t o0 = static_cast<int64_t>(blockIdx.x) * R;
-    if (o0 >= n_out) return;  // whole workgroup, before any barrier
-    const int lane = threadIdx.x & 63;
-    const int w = threadIdx.x >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const int col = (blockIdx.y * NW + w) * 32 + i;
-    if (order && *order_flag == 0) order = nullptr;
-    for (int t = threadIdx.x; t < R; t += NW * 64) {
-        const int64_t oo = o0 + t;
-        orow[t] = oo < n_out ? (order ? order[oo] : static_cast<int32_t>(oo)) : -1;
-    }
-    __syncthreads();
-    load_map_tile<R, NW * 64>(map, orow, K, threadIdx.x, mtile);
-    __syncthreads();
-    unsigned used = 0u;  // identical in every wave (same rows)
-    for (int k = h; k < K; k += 2) {
-        bool any = false;
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) any |= mtile[(32 * rb + i) * K + k] >= 0;
-        const uint64_t b = __ballot(any);
-        used |= ((h ? (b >> 32) : (b & 0xffffffffull)) != 0ull) ? (1u << k) : 0u;
-    }
-    used = __builtin_amdgcn_readlane(used, 32) | __builtin_amdgcn_readlane(used, 0);
-    f32x16 acc[RB];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[rb][r] = 0.f;
-    const int nch = (cin + 31) >> 5;
-    const int s = blockIdx.z;
-    const int j0 = split_stage(used, nch, K, s, nsplit);
-    const int j1 = split_stage(used, nch, K, s + 1, nsplit);
-    const __bf16* zp = reinterpret_cast<const __bf16*>(g_zero_page);
-    // this wave's DMA share of one stage: instructions q = w, w + NW, ... of
-    // the NI (row block, plane, 16-row half) triples; map reads first, then the DMAs
-    auto issue = [&](int buf, int k, int c0, bool live) {
-        constexpr int NQ = (NI + NW - 1) / NW;
-        int32_t mq[NQ];
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            const int q = w + NW * t;
-            const int r = 32 * (q / (2 * NP)) + 16 * (q & 1) + (lane >> 2);
-            mq[t] = (q < NI && live) ? mtile[r * K + k] : -1;
-        }
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            const int q = w + NW * t;
-            if (q >= NI) continue;  // wave-uniform
-            const int rb = q / (2 * NP), pl = (q % (2 * NP)) >> 1;
-            const int r = 16 * (q & 1) + (lane >> 2);  // row within the block
-            const int c = c0 + 8 * ((lane & 3) ^ ((r >> 2) & 3));
-            const __bf16* ga = (mq[t] >= 0 && c < cin) ? ap + pl * plane_a + static_cast<int64_t>(mq[t]) * cin + c : zp;
-            glds16(reinterpret_cast<const float*>(ga),
-                   reinterpret_cast<float*>(&abuf[buf][rb][pl][16 * 32 * (q & 1)]));
-        }
-    };
-    auto bload = [&](bf16x8 (&nb)[NP][2], int k, int c0, bool live) {
-        const bool colv = live && col < cout;
-        const int64_t wo = (static_cast<int64_t>(k) * cout + (colv ? col : 0)) * cin;
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int c = c0 + 16 * h + 8 * t;
-                nb[pl][t] = *reinterpret_cast<const bf16x8*>((colv && c < cin) ? bp + pl * plane_b + wo + c : zp);
-            }
-    };
-    if (j0 < j1) {  // uniform over the workgroup
-        unsigned u = used;
-        for (int t = j0 / nch; t > 0; --t) u &= u - 1u;
-        int k = __builtin_ctz(u), c0 = (j0 % nch) * 32;
-        bf16x8 nb[NP][2];
-        issue(0, k, c0, true);
-        bload(nb, k, c0, true);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int j = j0; j < j1; ++j) {
-            const int buf = NB == 1 ? 0 : ((j - j0) & 1);
-            bf16x8 fa[RB][NP][2], fb[NP][2];
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const int slot = (2 * h + t) ^ ((i >> 2) & 3);
-                        fa[rb][pl][t] = *reinterpret_cast<const bf16x8*>(&abuf[buf][rb][pl][32 * i + 8 * slot]);
-                    }
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) fb[pl][t] = nb[pl][t];
-            c0 += 32;
-            if (c0 >= cin) {
-                c0 = 0;
-                u &= u - 1u;
-                k = u ? __builtin_ctz(u) : 0;
-            }
-            const bool live = j + 1 < j1;
-            // one buffer: this stage's fragments are out of LDS before the next DMA
-            if constexpr (NB == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            issue(NB == 1 ? 0 : buf ^ 1, k, c0, live);
-            bload(nb, k, c0, live);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)  // per accumulator: the order of mfma_stage_split
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) {
-                    if constexpr (NT == 6) {
-                        acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[rb][1][t], fb[1][t], acc[rb], 0, 0, 0);
-                        acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[rb][2][t], fb[0][t], acc[rb], 0, 0, 0);
-                        acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[rb][0][t], fb[2][t], acc[rb], 0, 0, 0);
-                    }
-                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[rb][1][t], fb[0][t], acc[rb], 0, 0, 0);
-                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[rb][0][t], fb[1][t], acc[rb], 0, 0, 0);
-                    acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[rb][0][t], fb[0][t], acc[rb], 0, 0, 0);
-                }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own share of stage j+1 landed
-            __syncthreads();  // every share landed; stage j's buffer free
-        }
+    if (nsplit > 1) {
+        split_store(acc, orow, h, col, s, n_out, cout, part);
+        return;
     }
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        if (nsplit > 1) {
-            split_store_finish(acc[rb], orow + 32 * rb, h, col, lane, s, nsplit, n_out, cout, part, counters,
-                               ((static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * NW + w) * RB + rb,
-                               oscale, bias, residual, out);
-            continue;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t orr = orow[32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h];
-            if (orr >= 0 && col < cout) {
-                float v = acc[rb][r];
-                if (oscale) v *= oscale[orr];
-                if (bias) v += bias[col];
-                if (residual) v += residual[orr * cout + col];
-                out[orr * cout + col] = v;
-            }
+    for (int r = 0; r < 16; ++r) {
+        const int64_t orr = orow[(r & 3) + 8 * (r >> 2) + 4 * h];
+        if (orr >= 0 && col < cout) {
+            float v = acc[r];
+            if (oscale) v *= oscale[orr];
+            if (bias) v += bias[col];
+            if (residual) v += residual[orr * cout + col];
+            out[orr * cout + col] = v;
         }
     }
 }
@@ -2160,10 +1655,12 @@ __global__ void split_reduce_kernel(const float* __restrict__ part, int nsplit, 
 // Split of the (offset, Cin-chunk) reduction across waves when the output
 // tiles alone cannot fill the chip (deep UNet levels: a few hundred rows, up to
 // 448 input channels): enough splits for ~kGemmTargetWaves waves, at least
-// kGemmMinStages stages each, partial sums bounded by kGemmSplitBytes.
+// kGemmMinStages stages each, partial sums bounded by kGemmSplitBytes, at
+// most kGemmMaxSplits (the reduce reads every slab).
 constexpr int64_t kGemmTargetWaves = 4096;
 constexpr int kGemmMinStages = 4;
 constexpr int64_t kGemmSplitBytes = int64_t(64) << 20;
+constexpr int64_t kGemmMaxSplits = 64;
 
 // Product precision of the gather-GEMMs (mfma_stage_split): 1 = exact
 // f32-input MFMA (default: IEEE f32 products, infinities kept), 0 = bf16x6
@@ -2189,28 +1686,11 @@ static int gemm_nt() {  // template argument of the kernels: 0 exact, 3, 6 split
 
 static int gemm_splits(int64_t n_out, int K, int cin, int cout) {
     if (n_out <= 0 || cout <= 0) return 1;
-    static const int64_t target = [] {
-        const char* e = std::getenv("O3DML_GEMM_TARGET_WAVES");
-        return e ? std::max<int64_t>(1, std::atoll(e)) : kGemmTargetWaves;
-    }();
     const int64_t tiles = ceil_div(n_out, 32) * ceil_div(cout, 32);
-    // O3DML_GEMM_NOSPLIT_TILES = v > 0 (A/B): no split once the output tiles
-    // number >= v (the partial slabs and the reduce launch vs occupancy)
-    static const int64_t nosplit = [] {
-        const char* e = std::getenv("O3DML_GEMM_NOSPLIT_TILES");
-        return e ? std::atoll(e) : 0;
-    }();
-    if (nosplit > 0 && tiles >= nosplit) return 1;
-    int64_t ns = ceil_div(target, tiles);
+    int64_t ns = ceil_div(kGemmTargetWaves, tiles);
     ns = std::min<int64_t>(ns, std::max<int64_t>(1, (static_cast<int64_t>(K) * ceil_div(cin, 32)) / kGemmMinStages));
     ns = std::min<int64_t>(ns, kGemmSplitBytes / (n_out * cout * static_cast<int64_t>(sizeof(float))));
-    // O3DML_GEMM_MAX_SPLITS (A/B): cap on the splits (the reduce reads every slab)
-    static const int64_t cap = [] {
-        const char* e = std::getenv("O3DML_GEMM_MAX_SPLITS");
-        const int64_t v = e ? std::atoll(e) : 64;
-        return v < 1 ? 1 : (v > 64 ? 64 : v);
-    }();
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(ns, cap)));
+    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(ns, kGemmMaxSplits)));
 }
 
 // Persistent grid of implicit_gemm_lds_kernel: O3DML_GEMM_PERSIST = v > 0
@@ -2248,27 +1728,6 @@ static size_t gemm_split_bytes(int64_t n_out, int K, int cin, int cout) {
     return ns > 1 ? ws_bytes<float>(ns * n_out * cout) : 0;
 }
 
-// Presplit operands (implicit_gemm_split_kernel) — OFF by default: measured
-// on the C4 3^3 map (tools/gemm_probe.py, profiles/r03/sparse_conv_presplit_ab.txt)
-// it is slower than the in-kernel split at every width and row blocking
-// (32->32: 78 vs 69.5 us, 128->128: 382 vs 367 us at its best RB = 2).  The
-// in-kernel split's VALU work hides under the MFMA / L2 latency; what bounds
-// these kernels is the L2 -> LDS / register traffic of the gathered rows and
-// the per-stage filter fragments, which the 6-B bf16 planes raise by 1.5x.
-// O3DML_GEMM_PRESPLIT=1 or o3dml_sparse_conv_set_presplit(1) turns it on.
-static bool g_presplit = [] {
-    const char* e = std::getenv("O3DML_GEMM_PRESPLIT");
-    return e ? std::atoi(e) != 0 : false;
-}();
-
-// presplit operand planes: 3 bf16 planes of the n_src x cin source rows and of
-// the K x cout x cin filters (0 while presplit is off)
-static size_t presplit_bytes(int64_t n_src, int K, int cin, int cout) {
-    if (!g_presplit) return 0;
-    return 3 * ws_bytes<uint16_t>(n_src * cin) + 3 * ws_bytes<uint16_t>(static_cast<int64_t>(K) * cout * cin);
-}
-
-// everything run_gemm may take from its workspace
 // Filters split once per call for the per-wave kernel (split_filters_kernel,
 // BS): the B operand's hi / mid / lo come from a 6-B-per-weight copy instead
 // of three roundings per stage in every wave.  O3DML_GEMM_BSPLIT=0 or
@@ -2281,8 +1740,94 @@ static size_t bsplit_bytes(int K, int cin, int cout) {
     return cin == 32 ? ws_bytes<uint16_t>(3 * static_cast<int64_t>(K) * cout * cin) : 0;
 }
 
-static size_t gemm_ws_bytes(int64_t n_out, int64_t n_src, int K, int cin, int cout) {
-    return gemm_split_bytes(n_out, K, cin, cout) + presplit_bytes(n_src, K, cin, cout) + bsplit_bytes(K, cin, cout);
+// everything run_gemm may take from its workspace
+static size_t gemm_ws_bytes(int64_t n_out, int K, int cin, int cout) {
+    return gemm_split_bytes(n_out, K, cin, cout) + bsplit_bytes(K, cin, cout);
+}
+
+// What the three MFMA GEMM kernels are launched with (one parameter list).
+struct GemmArgs {
+    hipStream_t st;
+    const int32_t *map, *order;
+    const int* order_flag;
+    int K;
+    int64_t n_out;
+    const float *src, *sscale, *pscale, *Wt;
+    int cin, cout;
+    const float *oscale, *bias;
+    float* out;
+    int ns;  // split-K slabs in part (1: none)
+    float* part;
+    GemmPrologue pre;
+    const float* residual;
+};
+template <auto Kern>
+static void gemm_go(const GemmArgs& a, dim3 grid, int threads) {
+    Kern<<<grid, threads, 0, a.st>>>(a.map, a.order, a.order_flag, a.K, a.n_out, a.src, a.sscale, a.pscale, a.Wt, a.cin,
+                                     a.cout, a.oscale, a.bias, a.out, a.ns, a.part, a.pre, a.residual);
+}
+
+// any cin (gemm_load's single-word gathers); exact f32 products in every mode
+static void launch_generic(const GemmArgs& a) {
+    const dim3 g(static_cast<unsigned>(ceil_div(a.n_out, 32 * (kGemmThreads / 64))),
+                 static_cast<unsigned>(ceil_div(a.cout, 32)), static_cast<unsigned>(a.ns));
+    if (a.pre.scale) gemm_go<implicit_gemm_kernel<true>>(a, g, kGemmThreads);
+    else gemm_go<implicit_gemm_kernel<false>>(a, g, kGemmThreads);
+}
+
+// cin % 4 == 0, cout >= 64: the workgroup's NW waves share the gathered rows
+static void launch_shared(const GemmArgs& a) {
+    const int nw = a.cout % 128 == 0 ? 4 : 2;
+    const dim3 g(static_cast<unsigned>(ceil_div(a.n_out, 32)), static_cast<unsigned>(ceil_div(a.cout, 32 * nw)),
+                 static_cast<unsigned>(a.ns));
+    const bool sc = a.sscale || a.pscale;
+#define O3DML_GEMM_SHARED(P, S, W)                                                                          \
+    switch (gemm_nt()) {                                                                                    \
+        case 0: gemm_go<implicit_gemm_shared_kernel<P, 0, W, S>>(a, g, W * 64); break;                      \
+        case 3: gemm_go<implicit_gemm_shared_kernel<P, 3, W, S>>(a, g, W * 64); break;                      \
+        default: gemm_go<implicit_gemm_shared_kernel<P, 6, W, S>>(a, g, W * 64); break;                     \
+    }
+    if (nw == 4) {
+        if (a.pre.scale) O3DML_GEMM_SHARED(true, false, 4)
+        else if (sc) O3DML_GEMM_SHARED(false, true, 4)
+        else O3DML_GEMM_SHARED(false, false, 4)
+    } else {
+        if (a.pre.scale) O3DML_GEMM_SHARED(true, false, 2)
+        else if (sc) O3DML_GEMM_SHARED(false, true, 2)
+        else O3DML_GEMM_SHARED(false, false, 2)
+    }
+#undef O3DML_GEMM_SHARED
+}
+
+template <auto Kern>
+static void lds_go(GemmArgs a, dim3 g) {  // on the persistent grid when the work exceeds the resident waves
+    const dim3 gg = persist_grid<Kern>(g, a.pre);
+    gemm_go<Kern>(a, gg, kGemmThreads);
+}
+// cin % 4 == 0, cout < 64: a wave per tile.  buf: buffer addressing (no
+// scales); bs: the filters were split (a.pre.wsplit; mode 0, buffer path)
+static void launch_lds(const GemmArgs& a, bool buf, bool bs) {
+    const dim3 g(static_cast<unsigned>(ceil_div(a.n_out, 32 * (kGemmThreads / 64))),
+                 static_cast<unsigned>(ceil_div(a.cout, 32)), static_cast<unsigned>(a.ns));
+#define O3DML_GEMM_LDS(P, S, B)                                                        \
+    switch (gemm_nt()) {                                                               \
+        case 0: lds_go<implicit_gemm_lds_kernel<P, 0, S, B>>(a, g); break;             \
+        case 3: lds_go<implicit_gemm_lds_kernel<P, 3, S, B>>(a, g); break;             \
+        default: lds_go<implicit_gemm_lds_kernel<P, 6, S, B>>(a, g); break;            \
+    }
+    if (bs) {
+        if (a.pre.scale) lds_go<implicit_gemm_lds_kernel<true, 6, false, true, true>>(a, g);
+        else lds_go<implicit_gemm_lds_kernel<false, 6, false, true, true>>(a, g);
+    } else if (a.sscale || a.pscale) {
+        O3DML_GEMM_LDS(false, true, false)
+    } else if (buf) {
+        if (a.pre.scale) O3DML_GEMM_LDS(true, false, true)
+        else O3DML_GEMM_LDS(false, false, true)
+    } else {
+        if (a.pre.scale) O3DML_GEMM_LDS(true, false, false)
+        else O3DML_GEMM_LDS(false, false, false)
+    }
+#undef O3DML_GEMM_LDS
 }
 
 static void run_gemm(hipStream_t st, const int32_t* map, const int32_t* order, const int* order_flag, int K,
@@ -2291,9 +1836,16 @@ static void run_gemm(hipStream_t st, const int32_t* map, const int32_t* order, c
                      Workspace ws, GemmPrologue pre = {nullptr, nullptr}, const float* residual = nullptr,
                      const int32_t* tmap = nullptr) {
     if (n_out == 0 || cout == 0) return;
+    O3DML_REQUIRE(pre.scale == nullptr || cin <= kPreMax, "sparse_conv: prologue needs cin <= %d", kPreMax);
+    // the fused forward (the prologue's only caller) has no importance / normalisation
+    O3DML_REQUIRE(pre.scale == nullptr || (sscale == nullptr && pscale == nullptr),
+                  "sparse_conv: prologue with row / pair scales");
+    TimedRegion tr("sparse_conv_gemm", st);  // the GEMM kernel alone (bench roofline)
+    if (use_small_cin(cin, cout) && !pre.scale) {
+        launch_small_cin(st, map, K, n_out, src, sscale, pscale, Wt, cin, cout, oscale, bias, residual, out);
+        return;
+    }
     pre.tmap = order && use_tile_map() ? tmap : nullptr;
-    const bool vec4 = (cin % 4) == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 &&
-                      (reinterpret_cast<uintptr_t>(Wt) % 16) == 0;
     int ns = gemm_splits(n_out, K, cin, cout);
     float* part = nullptr;
     if (ns > 1) {
@@ -2301,244 +1853,42 @@ static void run_gemm(hipStream_t st, const int32_t* map, const int32_t* order, c
         if (ws.base && ws.used + pb <= ws.size) part = ws.take<float>(static_cast<int64_t>(ns) * n_out * cout);
         else ns = 1;
     }
-    const dim3 g(static_cast<unsigned>(round8(ceil_div(n_out, 32 * (kGemmThreads / 64)))),
-                 static_cast<unsigned>(ceil_div(cout, 32)), static_cast<unsigned>(ns));
-    O3DML_REQUIRE(pre.scale == nullptr || cin <= kPreMax, "sparse_conv: prologue needs cin <= %d", kPreMax);
-    // split-K finished by each tile's last wave (split_store_finish); the wave
-    // tiles of every kernel variant number ceil(n_out / 32) x ceil(cout / 32)
-    // rounded up to whole workgroups
-    // OFF by default: neutral on the C4 layer (0.172-0.177 ms either way, same
-    // session) — kept selectable (O3DML_GEMM_FUSED_REDUCE=1), bit-identical
-    static const bool fused_reduce = [] {
-        const char* e = std::getenv("O3DML_GEMM_FUSED_REDUCE");
-        return e ? std::atoi(e) != 0 : false;
-    }();
-    uint32_t* counters = nullptr;
-    if (ns > 1 && fused_reduce)
-        counters = tile_counters(st, (ceil_div(n_out, 128) + 1) * 4 * (ceil_div(cout, 32) + 4));
-    const int nt_mode = gemm_nt();
-    if (g_presplit && nt_mode != 0 && vec4 && cin % 8 == 0 && pscale == nullptr && ws.base &&
-        ws.used + presplit_bytes(n_src, K, cin, cout) <= ws.size) {
-        // operands split once (implicit_gemm_split_kernel); the split passes
-        // belong to the GEMM's time
-        TimedRegion tr("sparse_conv_gemm", st);
-        const int64_t pa = n_src * cin, pbn = static_cast<int64_t>(K) * cout * cin;
-        __bf16* ap = reinterpret_cast<__bf16*>(ws.take<uint16_t>(3 * pa));
-        __bf16* bpl = reinterpret_cast<__bf16*>(ws.take<uint16_t>(3 * pbn));
-        auto planes = [](__bf16* b, int64_t n) {
-            return std::array<bf16x8*, 3>{reinterpret_cast<bf16x8*>(b), reinterpret_cast<bf16x8*>(b + n),
-                                          reinterpret_cast<bf16x8*>(b + 2 * n)};
-        };
-        const auto A = planes(ap, pa), B = planes(bpl, pbn);
-        if (n_src > 0) {
-            if (nt_mode == 6)
-                presplit_kernel<6><<<stream_grid(pa / 8, 256), 256, 0, st>>>(src, n_src, cin, pre.scale, pre.shift,
-                                                                             sscale, A[0], A[1], A[2]);
-            else
-                presplit_kernel<3><<<stream_grid(pa / 8, 256), 256, 0, st>>>(src, n_src, cin, pre.scale, pre.shift,
-                                                                             sscale, A[0], A[1], A[2]);
-            O3DML_LAUNCH_CHECK();
-        }
-        if (nt_mode == 6)
-            presplit_kernel<6><<<stream_grid(pbn / 8, 256), 256, 0, st>>>(Wt, static_cast<int64_t>(K) * cout, cin,
-                                                                          nullptr, nullptr, nullptr, B[0], B[1], B[2]);
-        else
-            presplit_kernel<3><<<stream_grid(pbn / 8, 256), 256, 0, st>>>(Wt, static_cast<int64_t>(K) * cout, cin,
-                                                                          nullptr, nullptr, nullptr, B[0], B[1], B[2]);
-        O3DML_LAUNCH_CHECK();
-        const int nw = cout >= 128 && cout % 128 == 0 ? 4 : (cout >= 64 ? 2 : 1);
-        static const int env_rb = [] {
-            const char* e = std::getenv("O3DML_GEMM_SPLIT_RB");
-            return e ? std::atoi(e) : 0;
-        }();
-        // row blocks per tile: each B fragment (the filters, streamed from L2
-        // per stage) feeds RB accumulators
-        const int rb = env_rb == 1 || env_rb == 2 || env_rb == 4 ? env_rb : 2;
-        const dim3 gs(static_cast<unsigned>(ceil_div(n_out, 32 * rb)), static_cast<unsigned>(ceil_div(cout, 32 * nw)),
-                      static_cast<unsigned>(ns));
-#define O3DML_GEMM_SP(NT, W, B)                                                                                   \
-    implicit_gemm_split_kernel<NT, W, B><<<gs, W * 64, 0, st>>>(map, order, order_flag, K, n_out, ap, pa, bpl,    \
-                                                                 pbn, cin, cout, oscale, bias, out, ns, part,      \
-                                                                 residual, counters)
-#define O3DML_GEMM_SP_W(NT, B)                                                                     \
-    do {                                                                                           \
-        if (nw == 4) O3DML_GEMM_SP(NT, 4, B); else if (nw == 2) O3DML_GEMM_SP(NT, 2, B); else O3DML_GEMM_SP(NT, 1, B); \
-    } while (0)
-#define O3DML_GEMM_SP_RB(NT)                                                                  \
-    do {                                                                                      \
-        if (rb == 4) O3DML_GEMM_SP_W(NT, 4); else if (rb == 2) O3DML_GEMM_SP_W(NT, 2); else O3DML_GEMM_SP_W(NT, 1); \
-    } while (0)
-        if (nt_mode == 6) O3DML_GEMM_SP_RB(6); else O3DML_GEMM_SP_RB(3);
-#undef O3DML_GEMM_SP_RB
-#undef O3DML_GEMM_SP_W
-#undef O3DML_GEMM_SP
-        O3DML_LAUNCH_CHECK();
-        tr.end();
-        if (ns > 1 && !counters) {
-            split_reduce_kernel<<<stream_grid(n_out * cout, 256), 256, 0, st>>>(part, ns, n_out, cout, oscale, bias,
-                                                                               residual, out);
-            O3DML_LAUNCH_CHECK();
-        }
-        return;
-    }
-#define O3DML_GEMM_LAUNCH(V, P)                                                                                    \
-    implicit_gemm_kernel<V, P><<<g, kGemmThreads, 0, st>>>(map, order, order_flag, K, n_out, src, sscale, pscale, Wt, cin, cout, oscale, \
-                                                           bias, out, ns, part, pre, residual, counters)
-    static const bool lds_path = [] {
-        const char* e = std::getenv("O3DML_GEMM_LDS");
-        return e ? std::atoi(e) != 0 : true;
-    }();
-    TimedRegion tr("sparse_conv_gemm", st);  // the GEMM kernel alone (bench roofline)
-    if (use_small_cin(cin, cout) && !pre.scale) {  // no split: tile counters (if any) stay untouched
-        launch_small_cin(st, map, K, n_out, src, sscale, pscale, Wt, cin, cout, oscale, bias, residual, out);
-        return;
-    }
-    static const bool breg = [] {
-        const char* e = std::getenv("O3DML_GEMM_BREG");
-        return e ? std::atoi(e) != 0 : true;
-    }();
-    static const bool shared_path = [] {
-        const char* e = std::getenv("O3DML_GEMM_SHARED");
-        return e ? std::atoi(e) != 0 : true;
-    }();
+    const bool vec4 = (cin % 4) == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 &&
+                      (reinterpret_cast<uintptr_t>(Wt) % 16) == 0;
     // buffer addressing (rows and filters through buffer resources): whole
     // 32-channel stages, every byte offset of the operands below the
     // resources' out-of-range sentinel
-    static const bool buf_path = [] {
-        const char* e = std::getenv("O3DML_GEMM_BUF");
-        return e ? std::atoi(e) != 0 : true;
-    }();
-    const bool buf_ok = buf_path && cin % 32 == 0 && static_cast<uint64_t>(n_src) * cin * 4 < kNoRow &&
+    const bool buf_ok = cin % 32 == 0 && static_cast<uint64_t>(n_src) * cin * 4 < kNoRow &&
                         static_cast<uint64_t>(K) * cout * cin * 4 < kNoRow - 64;
     if (buf_ok) {  // the resources cover exactly the operands
         pre.src_bytes = static_cast<uint32_t>(static_cast<uint64_t>(n_src) * cin * 4);
         pre.w_bytes = static_cast<uint32_t>(static_cast<uint64_t>(K) * cout * cin * 4);
     }
-    // the shared-A kernel with buffer addressing: neutral in the same-session
-    // A/B (64->96 -3 %, 128->128 +1-2 %: its row addresses are split over the
-    // NW waves already) — off unless O3DML_GEMM_SHARED_BUF=1
-    static const bool shared_buf = [] {
-        const char* e = std::getenv("O3DML_GEMM_SHARED_BUF");
-        return e ? std::atoi(e) != 0 : false;
-    }();
-    // O3DML_GEMM_NW1=1 (A/B): narrow outputs (cout < 64) on the shared-A
-    // kernel with ONE wave per workgroup — with O3DML_GEMM_RB=2 a wave of 64
-    // rows whose filter fragment feeds two accumulators
-    static const bool nw1 = [] {
-        const char* e = std::getenv("O3DML_GEMM_NW1");
-        return e ? std::atoi(e) != 0 : false;
-    }();
-    if (vec4 && lds_path && shared_path && (cout >= 64 || nw1)) {
-        // A tile shared by NW column-block waves (implicit_gemm_shared_kernel)
-        const int nw = cout < 64 ? 1 : ((cout % 128 == 0) ? 4 : 2);
-        static const int rb = [] {
-            const char* e = std::getenv("O3DML_GEMM_RB");  // 2 row blocks per wave: measured slower
-            return (e && std::atoi(e) == 2) ? 2 : 1;
-        }();
-        const dim3 gs(static_cast<unsigned>(round8(ceil_div(n_out, 32 * rb))),
-                      static_cast<unsigned>(ceil_div(cout, 32 * nw)), static_cast<unsigned>(ns));
-#define O3DML_GEMM_SH_SC(P, X, W, B, SCL)                                                                      \
-    implicit_gemm_shared_kernel<P, X, W, B, SCL><<<gs, W * 64, 0, st>>>(map, order, order_flag, K, n_out, src,   \
-                                                                        sscale, pscale, Wt, cin, cout, oscale,   \
-                                                                        bias, out, ns, part, pre, residual,      \
-                                                                        counters)
-#define O3DML_GEMM_SH_BUF(P, X, W, B)                                                                          \
-    implicit_gemm_shared_kernel<P, X, W, B, false, true><<<gs, W * 64, 0, st>>>(                               \
-            map, order, order_flag, K, n_out, src, sscale, pscale, Wt, cin, cout, oscale, bias, out, ns, part, pre, \
-            residual, counters)
-#define O3DML_GEMM_SH(P, X, W, B)                                     \
-    do {                                                              \
-        if (sscale || pscale) O3DML_GEMM_SH_SC(P, X, W, B, true);     \
-        else if (buf_ok && shared_buf) O3DML_GEMM_SH_BUF(P, X, W, B); \
-        else O3DML_GEMM_SH_SC(P, X, W, B, false);                     \
-    } while (0)
-#define O3DML_GEMM_SH_RB(P, X, W) \
-    if (rb == 2) O3DML_GEMM_SH(P, X, W, 2); else O3DML_GEMM_SH(P, X, W, 1);
-#define O3DML_GEMM_SH_NT(P, W)                          \
-    switch (gemm_nt()) {                                \
-        case 0: O3DML_GEMM_SH_RB(P, 0, W) break;        \
-        case 3: O3DML_GEMM_SH_RB(P, 3, W) break;        \
-        default: O3DML_GEMM_SH_RB(P, 6, W) break;       \
-    }
-        if (nw == 4) {
-            if (pre.scale) { O3DML_GEMM_SH_NT(true, 4) } else { O3DML_GEMM_SH_NT(false, 4) }
-        } else if (nw == 1) {
-            if (pre.scale) { O3DML_GEMM_SH_NT(true, 1) } else { O3DML_GEMM_SH_NT(false, 1) }
-        } else {
-            if (pre.scale) { O3DML_GEMM_SH_NT(true, 2) } else { O3DML_GEMM_SH_NT(false, 2) }
-        }
-#undef O3DML_GEMM_SH_RB
-#undef O3DML_GEMM_SH_NT
-#undef O3DML_GEMM_SH
-#undef O3DML_GEMM_SH_SC
-#undef O3DML_GEMM_SH_BUF
-    } else if (vec4 && lds_path) {
-#define O3DML_GEMM_LDS_GO(...)                                                                                   \
-    do {                                                                                                         \
-        GemmPrologue pp = pre;                                                                                   \
-        const dim3 gg = persist_grid<__VA_ARGS__>(g, pp);                                                        \
-        __VA_ARGS__<<<gg, kGemmThreads, 0, st>>>(map, order, order_flag, K, n_out, src, sscale, pscale, Wt, cin, \
-                                                 cout, oscale, bias, out, ns, part, pp, residual, counters);     \
-    } while (0)
-#define O3DML_GEMM_LDS_SC(P, BR, X, SCL) O3DML_GEMM_LDS_GO(implicit_gemm_lds_kernel<P, BR, X, SCL>)
-#define O3DML_GEMM_LDS(P, BR, X)                                      \
-    do {                                                              \
-        if (sscale || pscale) O3DML_GEMM_LDS_SC(P, BR, X, true);      \
-        else if (BR && buf_ok) O3DML_GEMM_LDS_BUF(P, X);              \
-        else O3DML_GEMM_LDS_SC(P, BR, X, false);                      \
-    } while (0)
-#define O3DML_GEMM_LDS_BUF2(P, X, D) O3DML_GEMM_LDS_GO(implicit_gemm_lds_kernel<P, true, X, false, true, D>)
-#define O3DML_GEMM_LDS_BUF(P, X)                                 \
-    do {                                                         \
-        if (depth2) O3DML_GEMM_LDS_BUF2(P, X, 2);                \
-        else O3DML_GEMM_LDS_BUF2(P, X, 1);                       \
-    } while (0)
-        static const bool depth2 = [] {
-            const char* e = std::getenv("O3DML_GEMM_DEPTH");
-            return e ? std::atoi(e) == 2 : false;
-        }();
-        const int nt = gemm_nt();
-        const int64_t wn = static_cast<int64_t>(K) * cout * cin;
+    GemmArgs a{st,  map,  order,  order_flag, K,   n_out, src,  sscale, pscale,  Wt,
+               cin, cout, oscale, bias,       out, ns,    part, pre,    residual};
+    if (vec4 && cout >= 64) {
+        launch_shared(a);
+    } else if (vec4) {
         // one 32-channel chunk per offset only: at cin 32 the split copy saves
-        // 3 % (32->32, 32->16 layers), at cin 64 it cost 15 % (64->32;
-        // gpurun_out/r4s28, same session)
-        const bool bs = g_bsplit && nt == 6 && buf_ok && !depth2 && !sscale && !pscale && cin == 32 &&
+        // 3 % (32->32, 32->16 layers), at cin 64 it cost 15 % (64->32)
+        const int64_t wn = static_cast<int64_t>(K) * cout * cin;
+        const bool bs = g_bsplit && gemm_nt() == 6 && buf_ok && !sscale && !pscale && cin == 32 &&
                         static_cast<uint64_t>(wn) * 6u < kNoRow - 128 && ws.base &&
                         ws.used + bsplit_bytes(K, cin, cout) <= ws.size;
         if (bs) {
             bf16x8* w3 = reinterpret_cast<bf16x8*>(ws.take<uint16_t>(3 * wn));
             split_filters_kernel<<<stream_grid(wn / 8, 256), 256, 0, st>>>(Wt, wn / 8, w3);
             O3DML_LAUNCH_CHECK();
-            pre.wsplit = reinterpret_cast<const __bf16*>(w3);
-            pre.wsplit_bytes = static_cast<uint32_t>(wn * 6);
+            a.pre.wsplit = reinterpret_cast<const __bf16*>(w3);
+            a.pre.wsplit_bytes = static_cast<uint32_t>(wn * 6);
         }
-#define O3DML_GEMM_LDS_BS(P) O3DML_GEMM_LDS_GO(implicit_gemm_lds_kernel<P, true, 6, false, true, 1, true>)
-        if (nt == 6 && bs) {
-            if (pre.scale) O3DML_GEMM_LDS_BS(true); else O3DML_GEMM_LDS_BS(false);
-        } else if (nt == 6) {
-            if (pre.scale) O3DML_GEMM_LDS(true, true, 6); else O3DML_GEMM_LDS(false, true, 6);
-        } else if (nt == 3) {
-            if (pre.scale) O3DML_GEMM_LDS(true, true, 3); else O3DML_GEMM_LDS(false, true, 3);
-        } else if (pre.scale) {
-            if (breg) O3DML_GEMM_LDS(true, true, 0); else O3DML_GEMM_LDS(true, false, 0);
-        } else {
-            if (breg) O3DML_GEMM_LDS(false, true, 0); else O3DML_GEMM_LDS(false, false, 0);
-        }
-#undef O3DML_GEMM_LDS
-#undef O3DML_GEMM_LDS_SC
-#undef O3DML_GEMM_LDS_BUF
-#undef O3DML_GEMM_LDS_BUF2
-#undef O3DML_GEMM_LDS_BS
-#undef O3DML_GEMM_LDS_GO
-    } else if (pre.scale) {
-        if (vec4) O3DML_GEMM_LAUNCH(true, true); else O3DML_GEMM_LAUNCH(false, true);
+        launch_lds(a, buf_ok, bs);
     } else {
-        if (vec4) O3DML_GEMM_LAUNCH(true, false); else O3DML_GEMM_LAUNCH(false, false);
+        launch_generic(a);
     }
-#undef O3DML_GEMM_LAUNCH
     O3DML_LAUNCH_CHECK();
     tr.end();
-    if (ns > 1 && !counters) {
+    if (ns > 1) {
         split_reduce_kernel<<<stream_grid(n_out * cout, 256), 256, 0, st>>>(part, ns, n_out, cout, oscale, bias,
                                                                            residual, out);
         O3DML_LAUNCH_CHECK();
@@ -3111,10 +2461,10 @@ O3DML_API int o3dml_sparse_conv_forward_fused(const float* filters_t, int K, int
     O3DML_GUARD_END
 }
 
-// transposed filters, split-K partial sums and the presplit operand planes of
-// o3dml_sparse_conv_forward(_fused)
-O3DML_API size_t o3dml_sparse_conv_forward_workspace_size(int64_t n_out, int64_t n_in, int K, int cin, int cout) {
-    return ws_bytes<float>(static_cast<int64_t>(K) * cin * cout) + gemm_ws_bytes(n_out, n_in, K, cin, cout);
+// transposed filters, split-K partial sums and the split-filter copy of
+// o3dml_sparse_conv_forward(_fused); n_in is unused (kept for ABI stability)
+O3DML_API size_t o3dml_sparse_conv_forward_workspace_size(int64_t n_out, int64_t /*n_in*/, int K, int cin, int cout) {
+    return ws_bytes<float>(static_cast<int64_t>(K) * cin * cout) + gemm_ws_bytes(n_out, K, cin, cout);
 }
 
 // out [n_out, cout] = oscale * sum_k gather(inp) @ W[k] (+ bias).  filters:
@@ -3153,7 +2503,7 @@ static int dw_chunks(int64_t n_out, int K, int cin, int cout) {
 O3DML_API size_t o3dml_sparse_conv_backward_workspace_size(int64_t n_out, int64_t n_in, int K, int cin, int cout) {
     const int nchunk = dw_chunks(n_out, K, cin, cout);
     return ws_bytes<float>(static_cast<int64_t>(K) * cin * cout) + ws_bytes<float>(n_out * cout) +
-           gemm_ws_bytes(n_in, n_out, K, cout, cin) + ws_bytes<int64_t>(n_out * K) * 2 + ws_bytes<int32_t>(n_out * K) +
+           gemm_ws_bytes(n_in, K, cout, cin) + ws_bytes<int64_t>(n_out * K) * 2 + ws_bytes<int32_t>(n_out * K) +
            ws_bytes<int64_t>(K + 1) + ws_bytes<int64_t>(K + 2) +
            (nchunk > 1 ? ws_bytes<float>(static_cast<int64_t>(K) * (nchunk + 1) * cin * cout) : 0) +
            prim::scan_workspace_bytes(n_out * K);
@@ -3179,8 +2529,8 @@ O3DML_API int o3dml_sparse_conv_backward(const float* filters, int K, int cin, i
     float* wt = ws.take<float>(static_cast<int64_t>(K) * cin * cout);
     float* g = ws.take<float>(n_out * cout);  // unused slot kept for layout stability
     (void)g;
-    // the dIn GEMM's scratch (split-K partials, presplit planes)
-    const size_t gemm_bytes = gemm_ws_bytes(n_in, n_out, K, cout, cin);
+    // the dIn GEMM's scratch (split-K partials, split filters)
+    const size_t gemm_bytes = gemm_ws_bytes(n_in, K, cout, cin);
     Workspace gws(ws.base + ws.used, std::min(gemm_bytes, ws.size - ws.used));
     if (gemm_bytes) ws.take<uint8_t>(static_cast<int64_t>(gemm_bytes));
     const float* os = use_out_scale ? oscale : nullptr;
@@ -3258,17 +2608,11 @@ O3DML_API int o3dml_sparse_conv_backward(const float* filters, int K, int cin, i
     O3DML_GUARD_END
 }
 
-// ksize_host[3] = filter dims (k0,k1,k2) = (z,y,x) extents.
-// presplit operands on (1, default) / off (0); < 0 queries.  Returns the previous setting.
+// filters split once per call (BS kernels) on (1, default) / off (0); < 0
+// queries.  Returns the previous setting.
 O3DML_API int o3dml_sparse_conv_set_bsplit(int on) {
     const int prev = g_bsplit ? 1 : 0;
     if (on >= 0) g_bsplit = on != 0;
-    return prev;
-}
-
-O3DML_API int o3dml_sparse_conv_set_presplit(int on) {
-    const int prev = g_presplit ? 1 : 0;
-    if (on >= 0) g_presplit = on != 0;
     return prev;
 }
 
@@ -3281,6 +2625,7 @@ O3DML_API int o3dml_sparse_conv_set_exact(int exact) {
     return prev;
 }
 
+// ksize_host[3] = filter dims (k0,k1,k2) = (z,y,x) extents.
 O3DML_API int o3dml_sparse_conv_kernel_index(const float* inp_positions, const float* query_positions,
                                              const int32_t* neighbors_index, const int64_t* neighbors_row_splits,
                                              int64_t n_query, const int32_t* ksize_host, float voxel_size,

@@ -62,7 +62,7 @@ def _close(a, b, rtol=RTOL):
 
 
 @pytest.mark.parametrize("cin,cout", [(32, 32), (3, 16), (64, 96), (96, 224), (64, 128), (1, 32), (2, 16),
-                                      (4, 64), (3, 24)])
+                                      (4, 64), (3, 24), (6, 40)])
 def test_submanifold_conv_forward(cuda, cin, cout):
     from o3dml_amd import layers
     pos = _voxels(4000, 24, cin)
@@ -116,6 +116,76 @@ def test_deep_level_conv_split_k(cuda, n, ext, cin, cout):
     x = torch.relu(feat * scale + shift).cpu().numpy()
     t64, mag = _truth64(W, x, oi, ok, ors, conv.bias.detach().cpu().numpy())
     _close_elem(fused.cpu().numpy(), t64 + res.cpu().numpy(), mag + np.abs(res.cpu().numpy()))
+
+
+@pytest.mark.parametrize("cin,cout", [(6, 40), (16, 48), (32, 32), (64, 32), (64, 64), (128, 128)])
+def test_fused_prologue_all_precisions(cuda, cin, cout):
+    """The eval prologue (BN + ReLU on the gathered rows) and residual
+    epilogue in every product precision, on each GEMM kernel: generic (6 ->
+    40), per-wave (16 -> 48; 32 -> 32 and 64 -> 32 with buffer addressing, the
+    former in mode 0 in its split-filter form), shared-A with 2 and 4 waves
+    (64 -> 64, 128 -> 128).
+    ~250 rows: more than one workgroup, a partial last tile, split-K.
+    Modes 0 (bf16x6) and 1 (exact f32) per element against float64 — bf16x6
+    drops product terms <= 3 * 2^-24 |a b|, inside the 1e-6 floor on the
+    summed magnitudes; mode 2 (bf16x3, <= 2^-17 per product) within 1e-4 of
+    the largest output."""
+    from o3dml_amd import _lib, layers
+    lib = _lib.load()
+    pos = _voxels(300, 9, cin)
+    torch.manual_seed(2)
+    conv = layers.SparseConv(cin, cout, [3, 3, 3], use_bias=True).to(cuda)
+    torch.nn.init.normal_(conv.bias)
+    feat = torch.randn(len(pos), cin, device=cuda)
+    p = torch.from_numpy(pos).to(cuda)
+    scale = torch.rand(cin, device=cuda) + 0.5
+    shift = torch.randn(cin, device=cuda) * 0.1
+    res = torch.randn(len(pos), cout, device=cuda)
+    oi, ors, _ = O.fixed_radius_search(pos, pos, 1.5, metric="Linf")
+    ok = O.kernel_index(pos, pos, oi, ors, [3, 3, 3], 1.0)
+    x = torch.relu(feat.double() * scale.double() + shift.double()).cpu().numpy()
+    t64, mag = _truth64(conv.kernel.detach().cpu().numpy(), x, oi, ok, ors, conv.bias.detach().cpu().numpy())
+    t64, mag = t64 + res.cpu().numpy(), mag + np.abs(res.cpu().numpy())
+    prev = lib.o3dml_sparse_conv_set_exact(-1)
+    try:
+        for mode in (0, 1, 2):
+            lib.o3dml_sparse_conv_set_exact(mode)
+            with torch.no_grad():
+                fused = conv.forward_fused(feat, p, p, 1.0, pre=(scale, shift), residual=res).cpu().numpy()
+            if mode == 2:
+                _close(fused, t64)
+            else:
+                _close_elem(fused, t64, mag)
+    finally:
+        lib.o3dml_sparse_conv_set_exact(prev)
+
+
+@pytest.mark.parametrize("cin,cout", [(8, 24), (64, 64), (128, 128)])
+def test_importance_normalize_all_precisions(cuda, cin, cout):
+    """Row importance, pair importance and normalisation (the kernels' scale
+    loads) in every product precision: per-wave kernel (8 -> 24), shared-A
+    with 2 and 4 waves; against the oracle within the north-star 1e-4."""
+    from o3dml_amd import _lib, ops
+    lib = _lib.load()
+    pos = _voxels(300, 9, 21 + cin)
+    oi, ors, _ = O.fixed_radius_search(pos, pos, 1.5, metric="Linf")
+    ok = O.kernel_index(pos, pos, oi, ors, [3, 3, 3], 1.0)
+    rng = np.random.default_rng(5)
+    W = rng.standard_normal((3, 3, 3, cin, cout)).astype(np.float32)
+    x = rng.standard_normal((len(pos), cin)).astype(np.float32)
+    ii = rng.random(len(pos)).astype(np.float32)
+    ni = rng.random(len(oi)).astype(np.float32)
+    ref = O.sparse_conv(W, x, oi, ok, ors, inp_importance=ii, neighbors_importance=ni, normalize=True)
+    prev = lib.o3dml_sparse_conv_set_exact(-1)
+    try:
+        for mode in (0, 1, 2):
+            lib.o3dml_sparse_conv_set_exact(mode)
+            out = ops.sparse_conv(torch.from_numpy(W).to(cuda), torch.from_numpy(x).to(cuda), torch.from_numpy(ii),
+                                  torch.from_numpy(oi), torch.from_numpy(ok), torch.from_numpy(ni),
+                                  torch.from_numpy(ors), normalize=True)
+            _close(out.cpu().numpy(), ref)
+    finally:
+        lib.o3dml_sparse_conv_set_exact(prev)
 
 
 def test_strided_and_transposed_conv(cuda):
@@ -258,7 +328,7 @@ def test_lattice_rulebook_falls_back_off_lattice(cuda):
     _close(out.cpu().numpy(), ref + conv.bias.detach().cpu().numpy())
 
 
-@pytest.mark.parametrize("cin,cout", [(32, 32), (64, 128), (3, 48)])
+@pytest.mark.parametrize("cin,cout", [(32, 32), (64, 128), (3, 48), (16, 48), (96, 224), (64, 32)])
 def test_bf16_split_products_match_exact_f32(cuda, cin, cout):
     """Product precisions of the gather-GEMMs against a float64 reference:
     bf16x6 (each f32 operand as hi + mid + lo bf16, six products; opt-in)
@@ -419,36 +489,6 @@ def test_duplicate_kernel_indices(cuda, normalize, importance, cin):
     _close(gx.cpu().numpy(), gx64.numpy())
 
 
-@pytest.mark.parametrize("cin,cout", [(32, 32), (16, 48), (64, 64), (128, 128), (96, 224)])
-def test_presplit_operands_bitwise_equal(cuda, cin, cout):
-    """The presplit GEMM (operand hi/mid/lo planes made once per call,
-    implicit_gemm_split_kernel) against the in-kernel split
-    (implicit_gemm_lds/shared_kernel): the same split values and MFMA order,
-    so forward, dIn and dW are bitwise identical, in bf16x6 and bf16x3."""
-    from o3dml_amd import _lib, layers
-    lib = _lib.load()
-    vox = torch.from_numpy(_voxels(30000, 40, 3)).to(cuda)
-    torch.manual_seed(0)
-    conv = layers.SparseConv(cin, cout, [3, 3, 3], use_bias=True).to(cuda)
-    x = torch.randn((vox.shape[0], cin), device=cuda, requires_grad=True)
-    go = torch.randn((vox.shape[0], cout), device=cuda)
-    prev_mode = lib.o3dml_sparse_conv_set_exact(-1)
-    prev = lib.o3dml_sparse_conv_set_presplit(-1)
-    try:
-        for mode in (0, 2):
-            lib.o3dml_sparse_conv_set_exact(mode)
-            res = []
-            for on in (1, 0):
-                lib.o3dml_sparse_conv_set_presplit(on)
-                out = conv(x, vox, vox, 1.0)
-                res.append((out,) + torch.autograd.grad(out, (x, conv.kernel), go))
-            for a, b in zip(*res):
-                assert torch.equal(a, b), (mode, cin, cout)
-    finally:
-        lib.o3dml_sparse_conv_set_presplit(prev)
-        lib.o3dml_sparse_conv_set_exact(prev_mode)
-
-
 @pytest.mark.parametrize("cin,cout", [(32, 32), (64, 32), (32, 16), (96, 48), (16, 32)])
 def test_split_filters_bitwise_equal(cuda, cin, cout):
     """Filters split into bf16 hi / mid / lo once per call (split_filters_kernel,
@@ -469,6 +509,7 @@ def test_split_filters_bitwise_equal(cuda, cin, cout):
     inp = types.SimpleNamespace(point=[pos], feat=[torch.rand((20000, 3), generator=g).to(cuda)],
                                 batch_lengths=[20000])
     prev = lib.o3dml_sparse_conv_set_bsplit(-1)
+    prev_mode = lib.o3dml_sparse_conv_set_exact(0)  # bf16x6: the only precision with a BS form
     try:
         res = []
         for on in (1, 0):
@@ -479,72 +520,7 @@ def test_split_filters_bitwise_equal(cuda, cin, cout):
             assert torch.equal(a, b), (cin, cout)
     finally:
         lib.o3dml_sparse_conv_set_bsplit(prev)
-
-
-def test_presplit_fused_eval_bitwise_equal(cuda):
-    """SparseConvUnet eval (BN + ReLU prologue folded into the presplit
-    planes, residual epilogue): presplit on / off give identical logits."""
-    from o3dml_amd import _lib
-    from o3dml_amd.sparseconvnet import SparseConvUnet
-    import types
-    lib = _lib.load()
-    torch.manual_seed(0)
-    m = SparseConvUnet(multiplier=16, residual_blocks=True, conv_block_reps=1, num_classes=5).to(cuda).eval()
-    for mod in m.modules():
-        if isinstance(mod, torch.nn.BatchNorm1d):
-            mod.running_mean.uniform_(-0.5, 0.5)
-            mod.running_var.uniform_(0.5, 2.0)
-    g = torch.Generator().manual_seed(1)
-    pos = (torch.rand((20000, 3), generator=g) * 30).to(cuda)
-    inp = types.SimpleNamespace(point=[pos], feat=[torch.rand((20000, 3), generator=g).to(cuda)],
-                                batch_lengths=[20000])
-    prev = lib.o3dml_sparse_conv_set_presplit(-1)
-    try:
-        outs = []
-        for on in (1, 0):
-            lib.o3dml_sparse_conv_set_presplit(on)
-            with torch.no_grad():
-                outs.append(m(inp))
-        assert torch.equal(outs[0], outs[1])
-    finally:
-        lib.o3dml_sparse_conv_set_presplit(prev)
-
-
-def test_split_k_last_wave_finish_bitwise(cuda, tmp_path):
-    """Split-K GEMMs (deep SparseConvUnet levels) optionally finish in the
-    last-arriving wave of each tile (O3DML_GEMM_FUSED_REDUCE=1) instead of a
-    split_reduce_kernel launch: same slab order and epilogue, so
-    bit-identical (child processes: the switch is read once).  Eval (BN/ReLU prologue +
-    residual epilogue) and a training forward + backward (dIn split too)."""
-    import os
-    import subprocess
-    import sys
-    code = ("import sys, types, torch; sys.path.insert(0, 'open3d-ml_amd')\n"
-            "from o3dml_amd.sparseconvnet import SparseConvUnet\n"
-            "torch.manual_seed(0)\n"
-            "m = SparseConvUnet(multiplier=16, residual_blocks=True, conv_block_reps=1, num_classes=5).cuda()\n"
-            "g = torch.Generator().manual_seed(1)\n"
-            "pos = (torch.rand((30000, 3), generator=g) * torch.tensor([200., 200., 30.])).cuda()\n"
-            "inp = types.SimpleNamespace(point=[pos], feat=[torch.rand((30000, 3), generator=g).cuda()],"
-            " batch_lengths=[30000])\n"
-            "m.eval()\n"
-            "with torch.no_grad():\n"
-            "    a = m(inp)\n"
-            "m.train()\n"
-            "out = m(inp)\n"
-            "out.square().sum().backward()\n"
-            "torch.save([a.cpu(), out.detach().cpu()] + [p.grad.cpu() for p in m.parameters() if p.grad is not None],"
-            " sys.argv[1])\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for flag in ("1", "0"):
-        path = str(tmp_path / f"sc_reduce_{flag}.pt")
-        env = dict(os.environ, O3DML_GEMM_FUSED_REDUCE=flag)
-        subprocess.run([sys.executable, "-c", code, path], check=True, env=env, cwd=root, timeout=180)
-        outs.append(torch.load(path, weights_only=True))
-    assert len(outs[0]) == len(outs[1]) > 2
-    for a, b in zip(*outs):
-        assert torch.equal(a, b)
+        lib.o3dml_sparse_conv_set_exact(prev_mode)
 
 
 def test_gemm_schedules_bitwise(cuda, tmp_path):
