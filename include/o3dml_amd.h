@@ -378,6 +378,52 @@ size_t o3dml_nms_workspace_size(int64_t n);
 int o3dml_nms(const float* boxes, const float* scores, int64_t n, float nms_overlap_thresh, int64_t* keep,
               int64_t* keep_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PVCNN ops: replace open3d.ml.torch.ops.trilinear_devoxelize_forward /
+ * _backward (ml3d/torch/models/pvcnn.py:14, 37, 57) and the model's
+ * avg_voxelize (pvcnn.py:579-619).  Dense grid of r^3 voxels per batch item,
+ * r3 = r*r*r, voxel (x,y,z) at (x*r + y)*r + z; contiguous float32 unless
+ * noted.  Every sum runs in one fixed order (no float atomics): results are
+ * bitwise reproducible.  Limits (status code, before any launch): r >= 1,
+ * r3 <= 2^31 - 1, B*8*N (devoxelize) or B*N (voxelize) < 2^32,
+ * B*r3 < 2^32 - 1.
+ * devoxelize forward: coords [B,3,N] in grid units (clamped to [0, r-1]),
+ *   feat [B,C,r3] -> outs [B,C,N]; per axis lo = floor(a), d1 = a - lo,
+ *   d0 = 1 - d1, hi = lo + (d1 > 0); corner k = 4 bx + 2 by + bz has index
+ *   (x_bx*r + y_by)*r + z_bz and weight (dx_bx*dy_by)*dz_bz; outs = the eight
+ *   rounded products added left to right.  inds int32 / wgts [B,8,N] are
+ *   written when is_training and zero-filled otherwise.
+ * devoxelize backward: grad_feat[b,c,v] = sum over the entries e of inds[b]
+ *   equal to v, ascending flat position e = k*N + i, of wgts[e] *
+ *   grad_out[b,c,i]; entries outside [0, r3) contribute nothing; grad_feat
+ *   [B,C,r3] is fully written.  _backward_plan builds the per-voxel entry
+ *   lists into plan_ws (_backward_workspace_size bytes) once for every
+ *   _backward_planned call that shares inds; _backward does both.
+ * avg_voxelize: vox int32 [B,3,N] (clamped to [0, r-1]); _plan writes cnt
+ *   int32 [B,r3] (points per voxel) and the voxel plan (plan_ws of
+ *   _plan_workspace_size bytes, opaque), reused by every forward of the same
+ *   (vox, r); forward: grid[b,c,v] = (sum of feat[b,c,i] over the voxel's
+ *   points, ascending i) / max(cnt, 1), fully written; backward:
+ *   grad_feat[b,c,i] = grad_grid[b,c,h_i] / cnt[b,h_i]. ------------------- */
+int o3dml_trilinear_devoxelize_forward(const float* coords, const float* feat, int64_t B, int64_t C, int64_t N,
+                                       int64_t r, int is_training, float* outs, int32_t* inds, float* wgts,
+                                       void* stream);
+size_t o3dml_trilinear_devoxelize_backward_workspace_size(int64_t B, int64_t N, int64_t r);
+int o3dml_trilinear_devoxelize_backward_plan(const int32_t* inds, int64_t B, int64_t N, int64_t r, void* plan_ws,
+                                             size_t workspace_bytes, void* stream);
+int o3dml_trilinear_devoxelize_backward_planned(const float* grad_out, const float* wgts, const void* plan_ws,
+                                                int64_t B, int64_t C, int64_t N, int64_t r, float* grad_feat,
+                                                void* stream);
+int o3dml_trilinear_devoxelize_backward(const float* grad_out, const int32_t* inds, const float* wgts, int64_t B,
+                                        int64_t C, int64_t N, int64_t r, float* grad_feat, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+size_t o3dml_avg_voxelize_plan_workspace_size(int64_t B, int64_t N, int64_t r);
+int o3dml_avg_voxelize_plan(const int32_t* vox, int64_t B, int64_t N, int64_t r, int32_t* cnt, void* plan_ws,
+                            size_t workspace_bytes, void* stream);
+int o3dml_avg_voxelize_forward(const float* feat, const void* plan_ws, const int32_t* cnt, int64_t B, int64_t C,
+                               int64_t N, int64_t r, float* grid, void* stream);
+int o3dml_avg_voxelize_backward(const float* grad_grid, const int32_t* vox, const int32_t* cnt, int64_t B, int64_t C,
+                                int64_t N, int64_t r, float* grad_feat, void* stream);
+
 /* ---- sparse convolution: replaces open3d.ml.torch.ops.sparse_conv,
  * sparse_conv_transpose and their gradients, bound by layers.SparseConv /
  * layers.SparseConvTranspose (ml3d/torch/models/sparseconvnet.py:344-482;

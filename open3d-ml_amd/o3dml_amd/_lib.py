@@ -160,6 +160,16 @@ SIGNATURES = {
     "o3dml_three_interpolate_grad_det": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
     "o3dml_nms_workspace_size": (c_sz, [c_i64]),
     "o3dml_nms": (c_i32, [c_p, c_p, c_i64, c_f32, c_p, c_p, c_p, c_sz, c_p]),
+    # pvcnn.hip
+    "o3dml_trilinear_devoxelize_forward": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p]),
+    "o3dml_trilinear_devoxelize_backward_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
+    "o3dml_trilinear_devoxelize_backward_plan": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_sz, c_p]),
+    "o3dml_trilinear_devoxelize_backward_planned": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
+    "o3dml_trilinear_devoxelize_backward": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
+    "o3dml_avg_voxelize_plan_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
+    "o3dml_avg_voxelize_plan": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
+    "o3dml_avg_voxelize_forward": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
+    "o3dml_avg_voxelize_backward": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     # sparse_conv.hip
     "o3dml_sparse_conv_map_workspace_size": (c_sz, [c_i64, c_i64, c_i32]),
     "o3dml_sparse_conv_build_map": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_p, c_i32, c_p, c_p,

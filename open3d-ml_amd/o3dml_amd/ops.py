@@ -742,6 +742,79 @@ def three_interpolate_grad(grad_out, idx, weights, M):
 
 
 # ---------------------------------------------------------------------------
+# PVCNN ops (pvcnn.py:14, 37, 57)
+# ---------------------------------------------------------------------------
+def _f32_3d(name, t, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3:
+        raise RuntimeError(f"{name} must be float32 {what}, got "
+                           f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+
+
+def trilinear_devoxelize_forward(resolution, is_training, coords, features):
+    """Open3D ``ops.trilinear_devoxelize_forward`` (pvcnn.py:37): coords
+    [B,3,N] in grid units (clamped to [0, r-1]), features [B,C,r,r,r] or
+    [B,C,r^3] -> (outs [B,C,N], inds int32 [B,8,N], wgts [B,8,N]).  Corner
+    k = 4 bx + 2 by + bz; the high corner of an axis is lo + (frac > 0), so an
+    integer coordinate never indexes past the grid.  inds / wgts are written
+    when is_training and are zeros otherwise (the reference never reads them
+    in eval mode)."""
+    dev = gpu_device(coords, features)
+    r = int(resolution)
+    if r < 1:
+        raise RuntimeError(f"trilinear_devoxelize_forward: resolution must be >= 1, got {r}")
+    _f32_3d("coords", coords, "[B, 3, N]")
+    if coords.shape[1] != 3:
+        raise RuntimeError(f"coords must be float32 [B, 3, N], got {list(coords.shape)}")
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() not in (3, 5):
+        raise RuntimeError("features must be float32 [B, C, r, r, r] or [B, C, r^3], got "
+                           f"{getattr(features, 'dtype', type(features))} {list(getattr(features, 'shape', []))}")
+    B, _, N = coords.shape
+    C = features.shape[1]
+    spatial = tuple(features.shape[2:])
+    if features.shape[0] != B or spatial not in ((r, r, r), (r ** 3,)):
+        raise RuntimeError(f"features {list(features.shape)} do not match coords {list(coords.shape)} at "
+                           f"resolution {r}")
+    c = to_dev(coords.detach(), dev)
+    f = to_dev(features.detach(), dev)
+    outs = torch.empty((B, C, N), dtype=torch.float32, device=dev)
+    inds = torch.empty((B, 8, N), dtype=torch.int32, device=dev)
+    wgts = torch.empty((B, 8, N), dtype=torch.float32, device=dev)
+    _lib.call("o3dml_trilinear_devoxelize_forward", ptr(c), ptr(f), B, C, N, r, int(bool(is_training)), ptr(outs),
+              ptr(inds), ptr(wgts), stream_handle(dev))
+    return back_to(outs, coords), back_to(inds, coords), back_to(wgts, coords)
+
+
+def trilinear_devoxelize_backward(grad_y, indices, weights, resolution):
+    """Open3D ``ops.trilinear_devoxelize_backward`` (pvcnn.py:57): grad_y
+    [B,C,N], indices int32 / weights [B,8,N] -> [B,C,r^3].  Each voxel sums its
+    entries in ascending position of the [8,N] layout (per-voxel lists from a
+    stable sort; no float atomics): bitwise reproducible.  Indices outside
+    [0, r^3) contribute nothing.  Worst case: with every point on one corner
+    a single lane sums 8 N terms per channel."""
+    dev = gpu_device(grad_y, indices, weights)
+    r = int(resolution)
+    if r < 1:
+        raise RuntimeError(f"trilinear_devoxelize_backward: resolution must be >= 1, got {r}")
+    _f32_3d("grad_y", grad_y, "[B, C, N]")
+    _f32_3d("weights", weights, "[B, 8, N]")
+    B, C, N = grad_y.shape
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or tuple(indices.shape) != (B, 8, N):
+        raise RuntimeError(f"indices must be int32 [{B}, 8, {N}], got "
+                           f"{getattr(indices, 'dtype', type(indices))} {list(getattr(indices, 'shape', []))}")
+    if tuple(weights.shape) != (B, 8, N):
+        raise RuntimeError(f"weights must be float32 [{B}, 8, {N}], got {list(weights.shape)}")
+    g = to_dev(grad_y.detach(), dev)
+    i = to_dev(indices, dev)
+    w = to_dev(weights.detach(), dev)
+    out = torch.empty((B, C, r ** 3), dtype=torch.float32, device=dev)
+    if out.numel():
+        ws = workspace(_lib.load().o3dml_trilinear_devoxelize_backward_workspace_size(B, N, r), dev)
+        _lib.call("o3dml_trilinear_devoxelize_backward", ptr(g), ptr(i), ptr(w), B, C, N, r, ptr(out), ptr(ws),
+                  ws.numel(), stream_handle(dev))
+    return back_to(out, grad_y)
+
+
+# ---------------------------------------------------------------------------
 # sparse convolution (SURVEY §8a A12-A14) — see sparse_conv.py
 def nms(boxes, scores, nms_overlap_thresh):
     """Open3D ``ops.nms`` (objdet_helper.py:27, called at :346): rotated BEV NMS.
@@ -779,4 +852,4 @@ from .sparse_conv import sparse_conv, sparse_conv_transpose  # noqa: E402,F401
 __all__ = ["build_spatial_hash_table", "fixed_radius_search", "knn_search", "radius_search", "ragged_to_dense",
            "reduce_subarrays_sum", "voxelize", "grid_subsample", "calculate_grid", "furthest_point_sampling",
            "ball_query", "three_nn", "three_interpolate", "three_interpolate_grad", "nms", "sparse_conv",
-           "sparse_conv_transpose"]
+           "sparse_conv_transpose", "trilinear_devoxelize_forward", "trilinear_devoxelize_backward"]

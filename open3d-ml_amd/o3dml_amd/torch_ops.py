@@ -210,6 +210,30 @@ def _ti_backward(ctx, grad):
 three_interpolate.register_autograd(_ti_backward, setup_context=_ti_setup)
 
 
+# ----------------------------------------------------------------- PVCNN ops
+@_op("trilinear_devoxelize_forward")
+def trilinear_devoxelize_forward(resolution: int, is_training: bool, coords: Tensor, features: Tensor
+                                 ) -> tuple[Tensor, Tensor, Tensor]:
+    return ops.trilinear_devoxelize_forward(resolution, is_training, coords, features)
+
+
+@trilinear_devoxelize_forward.register_fake
+def _(resolution, is_training, coords, features):
+    iw = (coords.shape[0], 8, coords.shape[2])
+    return (coords.new_empty((coords.shape[0], features.shape[1], coords.shape[2])),
+            coords.new_empty(iw, dtype=torch.int32), coords.new_empty(iw))
+
+
+@_op("trilinear_devoxelize_backward")
+def trilinear_devoxelize_backward(grad_y: Tensor, indices: Tensor, weights: Tensor, resolution: int) -> Tensor:
+    return ops.trilinear_devoxelize_backward(grad_y, indices, weights, resolution)
+
+
+@trilinear_devoxelize_backward.register_fake
+def _(grad_y, indices, weights, resolution):
+    return grad_y.new_empty((grad_y.shape[0], grad_y.shape[1], resolution ** 3))
+
+
 @_op("nms")
 def nms(boxes: Tensor, scores: Tensor, nms_overlap_thresh: float) -> Tensor:
     return ops.nms(boxes, scores, nms_overlap_thresh)
@@ -299,4 +323,5 @@ sparse_conv_transpose.register_autograd(_sct_backward, setup_context=_sct_setup)
 
 OPS = ("build_spatial_hash_table", "fixed_radius_search", "knn_search", "radius_search", "ragged_to_dense",
        "reduce_subarrays_sum", "voxelize", "furthest_point_sampling", "ball_query", "three_nn", "three_interpolate",
-       "three_interpolate_grad", "nms", "sparse_conv", "sparse_conv_transpose")
+       "three_interpolate_grad", "nms", "sparse_conv", "sparse_conv_transpose", "trilinear_devoxelize_forward",
+       "trilinear_devoxelize_backward")

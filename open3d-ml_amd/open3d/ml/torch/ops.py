@@ -1,12 +1,13 @@
 """open3d.ml.torch.ops — hot-path ops backed by libo3dml_amd (HIP, gfx950).
 
-roi_pool (PointRCNN, roipool3d_utils.py:4) and trilinear_devoxelize_* (PVCNN,
-pvcnn.py:14) are out of scope: the reference imports them
-whenever a GPU is present, so the names exist and a call raises."""
+trilinear_devoxelize_forward / _backward (PVCNN, pvcnn.py:14) come from
+o3dml_amd.ops like every other op.  roi_pool (PointRCNN, roipool3d_utils.py:4)
+is out of scope: the reference imports it whenever a GPU is
+present, so the name exists and a call raises."""
 from o3dml_amd.ops import *  # noqa: F401,F403
 from o3dml_amd.ops import __all__ as _hot
 
-__all__ = list(_hot) + ["roi_pool", "trilinear_devoxelize_forward", "trilinear_devoxelize_backward"]
+__all__ = list(_hot) + ["roi_pool"]
 
 
 def _out_of_scope(name):
@@ -17,5 +18,3 @@ def _out_of_scope(name):
 
 
 roi_pool = _out_of_scope("roi_pool")
-trilinear_devoxelize_forward = _out_of_scope("trilinear_devoxelize_forward")
-trilinear_devoxelize_backward = _out_of_scope("trilinear_devoxelize_backward")
