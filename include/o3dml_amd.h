@@ -378,6 +378,36 @@ size_t o3dml_nms_workspace_size(int64_t n);
 int o3dml_nms(const float* boxes, const float* scores, int64_t n, float nms_overlap_thresh, int64_t* keep,
               int64_t* keep_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- pairwise rotated-box IoU: replaces open3d.ml.contrib.iou_bev_cuda /
+ * iou_3d_cuda / iou_bev_cpu / iou_3d_cpu (bound by ml3d/metrics/__init__.py:5-9
+ * and ml3d/datasets/utils/operations.py:7).  † Open3D IoUImpl, restated
+ * (positional contract, parity-unpinned like NMS):
+ *   mode 0, BEV: rows f32 [.,5] (cx, cy, w, l, ry) -> the NMS rectangle
+ *     (cx-w/2, cy-l/2, cx+w/2, cy+l/2, ry); IoU = inter / max(sa+sb-inter, 1e-8);
+ *   mode 1, 3D: rows f32 [.,7] (x, y, z, w, h, l, ry), camera frame with y the
+ *     bottom face: footprint (x, z, w, l, ry), vertical extent [y-h, y],
+ *     ov = area * max(min(ya,yb) - max(ya-ha, yb-hb), 0), v = w*h*l,
+ *     IoU = ov / max(va+vb-ov, 1e-8).
+ * Disjoint boxes give exactly 0.  Any float input is safe (bounded loops,
+ * nothing written outside out); values for NaN / inf / non-positive sizes are
+ * unspecified but deterministic. */
+/* Ragged batch in one launch (metrics/mAP.py:85-89 once per frame, and
+ * torch/models/point_rcnn.py:1423 once per batch item): frame f pairs rows
+ * [a_row_splits[f], a_row_splits[f+1]) of boxes_a [n_a,W] with rows
+ * [b_row_splits[f], b_row_splits[f+1]) of boxes_b [n_b,W]; its row-major
+ * [n_f, m_f] block starts at out[out_offsets[f]], out_offsets int64
+ * [n_batch+1] being the prefix sums of n_f*m_f and n_pairs (host value) their
+ * total = the length of out.  A single pair of sets is n_batch = 1.  No
+ * workspace, no synchronisation. */
+int o3dml_box_iou_ragged(const float* boxes_a, int64_t n_a, const int64_t* a_row_splits, const float* boxes_b,
+                         int64_t n_b, const int64_t* b_row_splits, const int64_t* out_offsets, int64_t n_batch,
+                         int64_t n_pairs, int mode, float* out, void* stream);
+/* Host version, one pair of sets (datasets/utils/operations.py:430 from
+ * data-loader workers; metrics/mAP.py:85-89 without a GPU): HOST pointers,
+ * out_host f32 [n,m] row-major.  Makes no HIP runtime call. */
+int o3dml_box_iou_host(const float* boxes_a_host, int64_t n, const float* boxes_b_host, int64_t m, int mode,
+                       float* out_host);
+
 /* ---- PVCNN ops: replace open3d.ml.torch.ops.trilinear_devoxelize_forward /
  * _backward (ml3d/torch/models/pvcnn.py:14, 37, 57) and the model's
  * avg_voxelize (pvcnn.py:579-619).  Dense grid of r^3 voxels per batch item,

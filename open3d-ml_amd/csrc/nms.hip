@@ -5,7 +5,8 @@
 // about their centre; overlap is the area of the convex intersection polygon
 // (edge crossings + contained corners, ordered by angle, shoelace area) and a
 // lower-scored box is dropped when IoU > threshold († Open3D IoUImpl /
-// NmsImpl, restated in oracle/o3d_oracle.c orc_nms).
+// NmsImpl, restated in oracle/o3d_oracle.c orc_nms).  The overlap geometry
+// (bev_iou) lives in box_iou.hpp, shared with the pairwise IoU kernel.
 //
 // Three launches, all on the caller's stream:
 //   1. rank kernel: stable descending score order (rank = #{higher score} +
@@ -17,119 +18,12 @@
 //   3. sweep kernel: one wavefront walks the sorted boxes in order, keeping
 //      the running "removed" bitmap (and, up to 64 KiB, the mask) in LDS and
 //      OR-ing in each kept box's row.
+#include "box_iou.hpp"
 #include "common.hpp"
 
 namespace o3dml {
 
 constexpr int kNmsBlock = 64;  // one wavefront == one 64-bit mask word
-constexpr float kNmsEps = 1e-8f;
-
-struct P2 {
-    float x, y;
-};
-
-__device__ __forceinline__ float cross3(P2 p1, P2 p2, P2 p0) {
-    return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
-}
-
-__device__ __forceinline__ bool rect_cross(P2 p1, P2 p2, P2 q1, P2 q2) {
-    return fminf(p1.x, p2.x) <= fmaxf(q1.x, q2.x) && fminf(q1.x, q2.x) <= fmaxf(p1.x, p2.x) &&
-           fminf(p1.y, p2.y) <= fmaxf(q1.y, q2.y) && fminf(q1.y, q2.y) <= fmaxf(p1.y, p2.y);
-}
-
-__device__ __forceinline__ bool in_box(const float* b, P2 p) {
-    const float margin = 1e-5f;
-    const float cx = (b[0] + b[2]) * 0.5f, cy = (b[1] + b[3]) * 0.5f;
-    const float c = cosf(-b[4]), s = sinf(-b[4]);
-    const float rx = (p.x - cx) * c + (p.y - cy) * s + cx;
-    const float ry = -(p.x - cx) * s + (p.y - cy) * c + cy;
-    return rx > b[0] - margin && rx < b[2] + margin && ry > b[1] - margin && ry < b[3] + margin;
-}
-
-// Segment p0-p1 against q0-q1; writes the crossing point.
-__device__ __forceinline__ bool seg_cross(P2 p1, P2 p0, P2 q1, P2 q0, P2& ans) {
-    if (!rect_cross(p0, p1, q0, q1)) return false;
-    const float s1 = cross3(q0, p1, p0), s2 = cross3(p1, q1, p0);
-    const float s3 = cross3(p0, q1, q0), s4 = cross3(q1, p1, q0);
-    if (!(s1 * s2 > 0.f && s3 * s4 > 0.f)) return false;
-    const float s5 = cross3(q1, p1, p0);
-    if (fabsf(s5 - s1) > kNmsEps) {
-        ans.x = (s5 * q0.x - s1 * q1.x) / (s5 - s1);
-        ans.y = (s5 * q0.y - s1 * q1.y) / (s5 - s1);
-    } else {
-        const float a0 = p0.y - p1.y, b0 = p1.x - p0.x, c0 = p0.x * p1.y - p1.x * p0.y;
-        const float a1 = q0.y - q1.y, b1 = q1.x - q0.x, c1 = q0.x * q1.y - q1.x * q0.y;
-        const float d = a0 * b1 - a1 * b0;
-        ans.x = (b0 * c1 - b1 * c0) / d;
-        ans.y = (a1 * c0 - a0 * c1) / d;
-    }
-    return true;
-}
-
-__device__ __forceinline__ void box_corners(const float* b, P2* c) {
-    const float cx = (b[0] + b[2]) * 0.5f, cy = (b[1] + b[3]) * 0.5f;
-    const float co = cosf(b[4]), si = sinf(b[4]);
-    const float xs[4] = {b[0], b[2], b[2], b[0]}, ys[4] = {b[1], b[1], b[3], b[3]};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        c[k].x = (xs[k] - cx) * co + (ys[k] - cy) * si + cx;
-        c[k].y = -(xs[k] - cx) * si + (ys[k] - cy) * co + cy;
-    }
-    c[4] = c[0];
-}
-
-__device__ float bev_iou(const float* a, const float* b) {
-    P2 ca[5], cb[5], pts[24];  // <= 16 edge crossings + 8 contained corners
-    box_corners(a, ca);
-    box_corners(b, cb);
-    int cnt = 0;
-    P2 ctr{0.f, 0.f};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            if (seg_cross(ca[i + 1], ca[i], cb[j + 1], cb[j], pts[cnt])) {
-                ctr.x += pts[cnt].x;
-                ctr.y += pts[cnt].y;
-                ++cnt;
-            }
-    for (int k = 0; k < 4; ++k) {
-        if (in_box(a, cb[k])) {
-            ctr.x += cb[k].x;
-            ctr.y += cb[k].y;
-            pts[cnt++] = cb[k];
-        }
-        if (in_box(b, ca[k])) {
-            ctr.x += ca[k].x;
-            ctr.y += ca[k].y;
-            pts[cnt++] = ca[k];
-        }
-    }
-    float area = 0.f;
-    if (cnt > 2) {
-        ctr.x /= cnt;
-        ctr.y /= cnt;
-        float ang[16];
-        for (int k = 0; k < cnt; ++k) ang[k] = atan2f(pts[k].y - ctr.y, pts[k].x - ctr.x);
-        for (int j = 0; j < cnt - 1; ++j)  // bubble sort, ascending angle
-            for (int i = 0; i < cnt - j - 1; ++i)
-                if (ang[i] > ang[i + 1]) {
-                    const P2 tp = pts[i];
-                    pts[i] = pts[i + 1];
-                    pts[i + 1] = tp;
-                    const float ta = ang[i];
-                    ang[i] = ang[i + 1];
-                    ang[i + 1] = ta;
-                }
-        for (int k = 0; k < cnt - 1; ++k) {
-            const float ux = pts[k].x - pts[0].x, uy = pts[k].y - pts[0].y;
-            const float vx = pts[k + 1].x - pts[0].x, vy = pts[k + 1].y - pts[0].y;
-            area += ux * vy - uy * vx;
-        }
-    }
-    const float inter = fabsf(area) * 0.5f;
-    const float sa = (a[2] - a[0]) * (a[3] - a[1]);
-    const float sb = (b[2] - b[0]) * (b[3] - b[1]);
-    return inter / fmaxf(sa + sb - inter, kNmsEps);
-}
 
 // Total-order sort key of a score: ascending floats map to ascending keys,
 // -0 and +0 share a key (they compare equal), every NaN maps to 0, below -inf.

@@ -7,7 +7,7 @@ thin shim in ``open3d-ml_amd/open3d/``), so ``open3d.ml.torch.ops`` /
 package and reference model code runs unchanged.  ``torch.ops.open3d.*``
 (TorchScript / torch.compile callers) is registered by ``o3dml_amd.torch_ops``.
 """
-from . import _lib, contrib, core, layers, ops  # noqa: F401
+from . import _lib, contrib, core, layers, metrics, ops  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -160,6 +160,9 @@ SIGNATURES = {
     "o3dml_three_interpolate_grad_det": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
     "o3dml_nms_workspace_size": (c_sz, [c_i64]),
     "o3dml_nms": (c_i32, [c_p, c_p, c_i64, c_f32, c_p, c_p, c_p, c_sz, c_p]),
+    # box_iou.hip, box_iou_host.cpp
+    "o3dml_box_iou_ragged": (c_i32, [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p]),
+    "o3dml_box_iou_host": (c_i32, [c_p, c_i64, c_p, c_i64, c_i32, c_p]),
     # pvcnn.hip
     "o3dml_trilinear_devoxelize_forward": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p]),
     "o3dml_trilinear_devoxelize_backward_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
