@@ -225,14 +225,6 @@ __device__ __forceinline__ int batch_of(int64_t i, const int64_t* __restrict__ s
     return lo;
 }
 
-// v_writelane: set lane LANE of v to the uniform value x (one instruction;
-// the lane select is an inline constant, the value an SGPR).
-template <int LANE>
-__device__ __forceinline__ int write_lane(int v, int x) {
-    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(x), "i"(LANE));
-    return v;
-}
-
 // Fourth word of a raw buffer resource on gfx950 (32-bit data format, no
 // swizzle/stride): used with __builtin_amdgcn_make_buffer_rsrc.
 constexpr int kBufferFlags = 0x00020000;

@@ -247,11 +247,15 @@ __device__ __forceinline__ uint32_t rdlane(int v, uint32_t lane) {
     return static_cast<uint32_t>(__builtin_amdgcn_readlane(v, static_cast<int>(lane)));
 }
 
-// lb[k] (uniform) into lane k for k = K..8
-template <int K>
-__device__ __forceinline__ int bin_lanes(int v, const uint32_t* lb) {
-    if constexpr (K < 9) return bin_lanes<K + 1>(write_lane<K>(v, static_cast<int>(lb[K])), lb);
-    return v;
+// Order-preserving int32 key of a float (a < b as floats <=> key(a) < key(b)
+// as ints, -0 below +0) and its inverse, the same bit operation: LDS has
+// exact integer min / max.
+__device__ __forceinline__ int32_t float_key(float f) {
+    const int32_t i = __float_as_int(f);
+    return i ^ ((i >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ uint32_t key_float(int32_t k) {
+    return static_cast<uint32_t>(k ^ ((k >> 31) & 0x7fffffff));
 }
 
 // MODE 0: every query of the (sorted) query array; its first kRowCap
@@ -354,93 +358,117 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
             // MODE 1 into a dense [M, dense_w] matrix: row qid starts at qid * dense_w
             if constexpr (MODE == 1) row = dense_w > 0 ? static_cast<int64_t>(qid) * dense_w : rs[qid];
         }
+        // 1. All groups of the chunk first (a group = the lanes with identical
+        //    nine bins): every lane learns its group, whether it leads it (its
+        //    lowest lane) and its qsh slot, in (group, slot) order; lane G of
+        //    vgrp describes group G.
         uint64_t todo = __builtin_amdgcn_ballot_w64(valid);
+        int ngrp = 0;
+        uint32_t goff = 0;   // queries in the groups so far
+        uint32_t mytag = 0;  // my group (bits 0-7), leader (bit 8), valid (bit 9), qsh slot (bits 16-23)
+        int vgrp = 0;        // lane G: size of group G (bits 0-7), its first slot (8-15), leader lane (16-23)
         while (todo) {
             const int leader = __builtin_ctzll(todo);
-            uint32_t lb[9];
             bool same = valid;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                lb[k] = rdlane(static_cast<int>(qb.b[k]), leader);
-                same = same && qb.b[k] == lb[k];
-            }
+            for (int k = 0; k < 9; ++k) same = same && qb.b[k] == rdlane(static_cast<int>(qb.b[k]), leader);
             const uint64_t gm = __builtin_amdgcn_ballot_w64(same);
-            // a group shares its buckets, hence its batch item
-            const uint32_t gbase = REL16 ? rdlane(static_cast<int>(pbase), leader) : 0u;
             todo &= ~gm;
-            const int ng = __popcll(gm);
-            __syncthreads();  // previous group done with qsh / cand
+            const uint32_t ng = static_cast<uint32_t>(__popcll(gm));
             if (same) {
                 const uint32_t slot = mbcnt64(gm);
-                qsh[slot] = q4;
-                if constexpr (MODE == 1) qrow[slot] = row;
+                mytag = static_cast<uint32_t>(ngrp) | (slot == 0 ? 0x300u : 0x200u) | ((goff + slot) << 16);
             }
-            // group bounding box: groups of <= 16 (nearly all) reduce the member
-            // slots qsh[0, ng) within one 16-lane DPP row, larger ones the whole wave
-            float lx, ly, lz, hx, hy, hz;
-            if (ng <= 16) {
+            if (lane == ngrp) vgrp = static_cast<int>(ng | (goff << 8) | (static_cast<uint32_t>(leader) << 16));
+            goff += ng;
+            ++ngrp;
+        }
+        uint32_t* const tab = reinterpret_cast<uint32_t*>(cand);
+        // 2. The queries into qsh, once per chunk
+        __syncthreads();  // previous chunk done with qsh / cand
+        if (valid) {
+            qsh[mytag >> 16] = q4;
+            if constexpr (MODE == 1) qrow[mytag >> 16] = row;
+        }
+        // 3. The groups in order.  Their bucket lists are built a batch at a
+        //    time, for the next (up to) seven groups in one pass: vst / vlen hold
+        //    the batch's lists one after the other, each followed by a zero entry,
+        //    and bit 9 t + k of km says that visited bin k of the batch's t-th
+        //    group is a live segment.
+        uint32_t vst = 0, vlen = 0;
+        uint64_t km = 0;
+        int gi = 0, nbat = 0;  // group within the batch, groups of the batch
+        for (int grp = 0; grp < ngrp; ++grp, ++gi) {
+            if (gi == nbat) {
+                // Bucket lists of groups grp .. grp + 6, empty and repeated bins
+                // dropped: lane 9 t + k takes visited bin k of group grp + t.
+                // The leaders publish their sorted bins and the members reduce the
+                // group's box (16 words per group in the candidate list, free
+                // here).  With the class directory, a
+                // bucket's classes whose box is out of reach of the group's box
+                // are skipped (box_box_dist: exact, see bucket_classes_kernel);
+                // one class left streams its sub-list, none skips the bucket,
+                // more stream it whole.
+                // Per group 16 words of tab: the box as order-preserving integer
+                // keys (min x, y, z, max x, y, z: LDS integer min / max over the
+                // members are exact), then the nine bins.
+                uint2* const seg = reinterpret_cast<uint2*>(cand) + 64;  // (start, length) per list entry
+                // The pass's lane arithmetic and constants are pinned inside it:
+                // hoisted out of the group loop they would sit in VGPRs across
+                // the stream and test loops, which have none to spare.
+                int bl = lane;
+                uint32_t kmax = INT32_MAX, kmin = static_cast<uint32_t>(INT32_MIN), zero = 0u;
+                asm volatile("" : "+v"(bl), "+v"(kmax), "+v"(kmin), "+v"(zero));
+                const int tg = (bl * 57) >> 9, tk = bl - 9 * tg;  // lane / 9, lane % 9
+                __syncthreads();  // previous group done with cand
+                const uint32_t rel = (mytag & 0xffu) - static_cast<uint32_t>(grp);
+                if ((mytag & 0x100u) != 0u && rel < 7u) {
+                    uint4* const tp = reinterpret_cast<uint4*>(tab) + 4 * rel;
+                    tp[0] = make_uint4(kmax, kmax, kmax, kmin);
+                    tp[1] = make_uint4(kmin, kmin, qb.b[0], qb.b[1]);
+                    tp[2] = make_uint4(qb.b[2], qb.b[3], qb.b[4], qb.b[5]);
+                    tp[3] = make_uint4(qb.b[6], qb.b[7], qb.b[8], zero);
+                }
+                seg[bl] = make_uint2(zero, zero);
                 __syncthreads();
-                const float4 v = lane < ng ? qsh[lane & 15] : far;
-                const float4 w = lane < ng ? v : make_float4(-inf, -inf, -inf, 0.f);
-                lx = row0_min_f(v.x), ly = row0_min_f(v.y), lz = row0_min_f(v.z);
-                hx = row0_max_f(w.x), hy = row0_max_f(w.y), hz = row0_max_f(w.z);
-            } else {
-                lx = wave_min_f(same ? q4.x : inf), ly = wave_min_f(same ? q4.y : inf),
-                lz = wave_min_f(same ? q4.z : inf);
-                hx = wave_max_f(same ? q4.x : -inf), hy = wave_max_f(same ? q4.y : -inf),
-                hz = wave_max_f(same ? q4.z : -inf);
-            }
-            // lane -> (query g, slice s)
-            // S = floor(64 / ng) lanes per query (not a power of two: 9 queries
-            // take 63 lanes, not 9 of 16 slots x 4); g = lane / S by the
-            // multiply-shift of the table, exact for lane < 64
-            const uint32_t split = kLaneSplit[ng];
-            const int S = static_cast<int>(split & 0xffu);
-            const int g = static_cast<int>((static_cast<uint32_t>(lane) * (split >> 8)) >> 16);
-            const int sl = lane - g * S;
-            __syncthreads();
-            float4 mq = far;  // lanes past the group test the far point: never a hit
-            int64_t mrow = 0;
-            if (g < ng) {
-                mq = qsh[g];
-                mrow = MODE == 0 ? static_cast<int64_t>(__float_as_uint(mq.w)) : qrow[g];
-            }
-            uint32_t cnt = 0;  // neighbours of query g so far (uniform over its S lanes)
-            const uint32_t row_b = static_cast<uint32_t>(mrow) * (2u * kRowCap);  // REL16: byte offset of the row
-            const uint64_t gmask = S == 64 ? ~0ull : (g < ng ? ((1ull << S) - 1ull) << (g * S) : 0ull);
-            const uint32_t gm_lo = static_cast<uint32_t>(gmask), gm_hi = static_cast<uint32_t>(gmask >> 32);
-            // Bucket list of the group in visit order, empty and repeated bins
-            // dropped: lane j < nbk holds the start (in pts, or in the class
-            // sub-lists p2) and the length of the j-th stream segment.  Built in
-            // parallel (lane k < 9 takes bin k) and compacted through the
-            // candidate list, free here.  With the class directory, a bucket's
-            // classes whose box is out of reach of the group's box are skipped
-            // (box_box_dist: exact, see bucket_classes_kernel); one class left
-            // streams its sub-list, none skips the bucket, more stream it whole.
-            uint32_t vst, vlen;
-            int nbk;
-            {
-                const uint32_t vb = static_cast<uint32_t>(bin_lanes<0>(-1, lb));
-                uint32_t s0 = 0, e0 = 0;
+                if ((mytag & 0x200u) != 0u && rel < 7u) {
+                    const float4 me = qsh[mytag >> 16];
+                    int32_t* const k = reinterpret_cast<int32_t*>(tab) + 16 * rel;
+                    const int32_t kx = float_key(me.x), ky = float_key(me.y), kz = float_key(me.z);
+                    __hip_atomic_fetch_min(k + 0, kx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_min(k + 1, ky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_min(k + 2, kz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_max(k + 3, kx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_max(k + 4, ky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_max(k + 5, kz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                __syncthreads();
+                // lanes of tasks past the last group take the first group's first
+                // bin: a valid address, and `first` below gives them length 0
+                const bool task_ok = tg < 7 && grp + tg < ngrp;
+                const uint32_t* const tq = tab + 16 * tg;
+                const uint32_t vb = tab[task_ok ? 16 * tg + 6 + tk : 6];
+                const uint32_t prev = tq[5 + tk];  // the bin before mine (tk > 0)
+                const uint4 b0 = reinterpret_cast<const uint4*>(tq)[0];
+                const uint2 b1 = reinterpret_cast<const uint2*>(tq)[2];
                 // the bin's bounds and its class directory entry in flight together
-                // (the directory exists for every bin when `sub`)
+                // (the directory exists for every bin when `sub`): no load under a
+                // lane condition
+                const uint32_t s0 = cs[vb], e0 = cs[vb + 1];
                 uint4 w0 = {}, w1 = {}, w2 = {}, w3 = {}, w4 = {}, w5 = {};
-                if (lane < 9) {
-                    s0 = cs[vb];
-                    e0 = cs[vb + 1];
-                    if (sub) {
-                        const uint4* dp = reinterpret_cast<const uint4*>(dir + static_cast<size_t>(vb) * kDirWords);
-                        w0 = dp[0], w1 = dp[1], w2 = dp[2], w3 = dp[3], w4 = dp[4], w5 = dp[5];
-                    }
+                if (sub) {
+                    const uint4* dp = reinterpret_cast<const uint4*>(dir + static_cast<size_t>(vb) * kDirWords);
+                    w0 = dp[0], w1 = dp[1], w2 = dp[2], w3 = dp[3], w4 = dp[4], w5 = dp[5];
                 }
                 // the bins are sorted: a repeat sits right after its first copy
-                const uint32_t prev = static_cast<uint32_t>(
-                        __builtin_amdgcn_update_dpp(-1, static_cast<int>(vb), 0x111, 0xF, 0xF, false));  // row_shr:1
-                const bool first = lane < 9 && e0 > s0 && prev != vb;
+                const bool first = task_ok && e0 > s0 && (tk == 0 || prev != vb);
                 uint32_t st = s0, ln = e0 - s0;
                 if (first && sub) {
-                    const uint32_t n0 = w0.x, n1 = w0.y, n2 = ln - n0 - n1;
                     auto f = [](uint32_t u) { return __uint_as_float(u); };
+                    auto kf = [](uint32_t k) { return __uint_as_float(key_float(static_cast<int32_t>(k))); };
+                    const float lx = kf(b0.x), ly = kf(b0.y), lz = kf(b0.z), hx = kf(b0.w), hy = kf(b1.x),
+                                hz = kf(b1.y);
+                    const uint32_t n0 = w0.x, n1 = w0.y, n2 = ln - n0 - n1;
                     const bool r0 = n0 > 0 && box_box_dist<METRIC>(f(w1.x), f(w1.y), f(w1.z), f(w1.w), f(w2.x),
                                                                    f(w2.y), lx, ly, lz, hx, hy, hz) <= thr;
                     const bool r1 = n1 > 0 && box_box_dist<METRIC>(f(w2.z), f(w2.w), f(w3.x), f(w3.y), f(w3.z),
@@ -457,21 +485,63 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
                     }
                 }
                 const bool live = first && ln > 0;
-                const uint64_t km = __builtin_amdgcn_ballot_w64(live);
-                nbk = __popcll(km);
-                uint32_t* tab = reinterpret_cast<uint32_t*>(cand);
-                if (live) {
-                    const uint32_t j = mbcnt64(km);
-                    tab[j] = st;
-                    tab[16 + j] = ln;
-                }
+                km = __builtin_amdgcn_ballot_w64(live);
+                // Lists packed in group order with one zero entry after each, so
+                // the cursor's look at "the entry after the last" never sees the
+                // next group's first: entry = live tasks before mine + my group.
+                // 7 lists and their zeros fit 64 lanes up to 57 segments (a list
+                // has 9 only in a rounding corner case); beyond, the seventh
+                // group waits for the next batch (6 x 10 always fit).
+                nbat = __popcll(km) > 57 ? 6 : min(7, ngrp - grp);
+                if (live && tg < nbat) seg[mbcnt64(km) + tg] = make_uint2(st, ln);
                 __syncthreads();
-                vst = lane < nbk ? tab[lane] : 0u;
-                vlen = lane < nbk ? tab[16 + lane] : 0u;
+                const uint2 sg = seg[bl];
+                vst = sg.x, vlen = sg.y;
                 __syncthreads();
+                gi = 0;
             }
+            const uint32_t ginfo = rdlane(vgrp, static_cast<uint32_t>(grp));
+            const int ng = static_cast<int>(ginfo & 0xffu);
+            const uint32_t gslot = (ginfo >> 8) & 0xffu, leader = ginfo >> 16;
+            // a group shares its buckets, hence its batch item
+            const uint32_t gbase = REL16 ? rdlane(static_cast<int>(pbase), leader) : 0u;
+            // group bounding box over the member slots qsh[gslot, gslot + ng): groups
+            // of <= 16 (nearly all) within one 16-lane DPP row, larger ones the whole wave
+            float lx, ly, lz, hx, hy, hz;
+            if (ng <= 16) {
+                const float4 v = lane < ng ? qsh[gslot + (lane & 15)] : far;
+                const float4 w = lane < ng ? v : make_float4(-inf, -inf, -inf, 0.f);
+                lx = row0_min_f(v.x), ly = row0_min_f(v.y), lz = row0_min_f(v.z);
+                hx = row0_max_f(w.x), hy = row0_max_f(w.y), hz = row0_max_f(w.z);
+            } else {
+                const float4 v = lane < ng ? qsh[gslot + lane] : far;
+                const float4 w = lane < ng ? v : make_float4(-inf, -inf, -inf, 0.f);
+                lx = wave_min_f(v.x), ly = wave_min_f(v.y), lz = wave_min_f(v.z);
+                hx = wave_max_f(w.x), hy = wave_max_f(w.y), hz = wave_max_f(w.z);
+            }
+            // lane -> (query g, slice s)
+            // S = floor(64 / ng) lanes per query (not a power of two: 9 queries
+            // take 63 lanes, not 9 of 16 slots x 4); g = lane / S by the
+            // multiply-shift of the table, exact for lane < 64
+            const uint32_t split = kLaneSplit[ng];
+            const int S = static_cast<int>(split & 0xffu);
+            const int g = static_cast<int>((static_cast<uint32_t>(lane) * (split >> 8)) >> 16);
+            const int sl = lane - g * S;
+            float4 mq = far;  // lanes past the group test the far point: never a hit
+            int64_t mrow = 0;
+            if (g < ng) {
+                mq = qsh[gslot + g];
+                mrow = MODE == 0 ? static_cast<int64_t>(__float_as_uint(mq.w)) : qrow[gslot + g];
+            }
+            uint32_t cnt = 0;  // neighbours of query g so far (uniform over its S lanes)
+            const uint32_t row_b = static_cast<uint32_t>(mrow) * (2u * kRowCap);  // REL16: byte offset of the row
+            const uint64_t gmask = S == 64 ? ~0ull : (g < ng ? ((1ull << S) - 1ull) << (g * S) : 0ull);
+            const uint32_t gm_lo = static_cast<uint32_t>(gmask), gm_hi = static_cast<uint32_t>(gmask >> 32);
+            // the group's list: entries [bk, nbk) of vst / vlen
+            int bk = __popcll(km & ((1ull << (9 * gi)) - 1ull)) + gi;
+            int nbk = bk + __popcll((km >> (9 * gi)) & 0x1ffull);
 #if O3DML_DIAG == 2
-            nbk = 0;  // diagnostics: grouping and bucket tables only, no streaming
+            nbk = bk;  // diagnostics: grouping and bucket tables only, no streaming
 #endif
             // stop filling while the next round (and the test padding) might not fit
             const int fill_lim = kCandCap - 64 * kStreamU - (S - 1);
@@ -479,7 +549,6 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
             // round of 64 lanes takes the rest of bucket bk (lanes < t) and the
             // head of bucket bk + 1, never more than two buckets; lanes past the
             // group's buckets (or past bucket bk + 1) read the far sentinel.
-            int bk = 0;
             uint32_t boff = 0;
             auto round_src = [&]() -> uint32_t {
                 if (bk >= nbk) return n_pts;
