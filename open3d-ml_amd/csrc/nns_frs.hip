@@ -120,67 +120,18 @@ constexpr int kStreamU = O3DML_STREAM_U;  // 64-point loads in flight per lane w
 // 4 KiB + 1 KiB of query slots keeps 32 waves per CU (LDS no tighter than the
 // 64-VGPR limit of 8 waves per SIMD)
 constexpr int kCandCap = 256;
+// Slot table of the run leaders of a chunk (words of the candidate list, past
+// the group tables and segment list of the set-up): 512 slots
+constexpr uint32_t kRunSlot0 = 512, kRunSlots = 512;
 
-// Wave-wide float min / max: DPP within rows of 16 lanes, then the 4 row
-// results through v_readlane (uniform result, no LDS round trip).
-// O3DML_FRS_DPPMIN (default): each step is ONE v_min_f32_dpp / v_max_f32_dpp
-// (the DPP source folded into the VOP2 min/max); fminf through a
-// v_mov_b32_dpp costs that mov plus two canonicalising v_max_f32 (fminf's
-// signalling-NaN rule) per step — 5 instructions instead of 1.  The s_nop
-// covers the VALU-write -> DPP-read hazard inside the asm block.
-#ifndef O3DML_FRS_DPPMIN
-#define O3DML_FRS_DPPMIN 1
-#endif
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-#define O3DML_DPP_STEP(NAME, OP, CTRL)                                                                   \
-    __device__ __forceinline__ float NAME(float v) {                                                    \
-        float r;                                                                                        \
-        asm volatile("s_nop 1\n\t" OP "_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf"            \
-                     : "=v"(r)                                                                          \
-                     : "v"(v));                                                                         \
-        return r;                                                                                       \
-    }
-O3DML_DPP_STEP(dmin_q1, "v_min_f32", "quad_perm:[1,0,3,2]")
-O3DML_DPP_STEP(dmin_q2, "v_min_f32", "quad_perm:[2,3,0,1]")
-O3DML_DPP_STEP(dmin_hm, "v_min_f32", "row_half_mirror")
-O3DML_DPP_STEP(dmin_rm, "v_min_f32", "row_mirror")
-O3DML_DPP_STEP(dmax_q1, "v_max_f32", "quad_perm:[1,0,3,2]")
-O3DML_DPP_STEP(dmax_q2, "v_max_f32", "quad_perm:[2,3,0,1]")
-O3DML_DPP_STEP(dmax_hm, "v_max_f32", "row_half_mirror")
-O3DML_DPP_STEP(dmax_rm, "v_max_f32", "row_mirror")
-#undef O3DML_DPP_STEP
-// min (MAX: max) over each row of 16 lanes, in every lane of the row
-template <bool MAX>
-__device__ __forceinline__ float row_ext_f(float v) {
-#if O3DML_FRS_DPPMIN
-    if constexpr (MAX) return dmax_rm(dmax_hm(dmax_q2(dmax_q1(v))));
-    return dmin_rm(dmin_hm(dmin_q2(dmin_q1(v))));
-#else
-    auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); };
-    v = op(v, dpp_f<0xB1>(v));   // quad_perm(1,0,3,2)
-    v = op(v, dpp_f<0x4E>(v));   // quad_perm(2,3,0,1)
-    v = op(v, dpp_f<0x141>(v));  // row_half_mirror
-    v = op(v, dpp_f<0x140>(v));  // row_mirror
-    return v;
-#endif
+// The value of the lane to the left (DPP wave_shr:1); lane 0 keeps its own.
+__device__ __forceinline__ uint32_t left_lane(uint32_t v) {
+    return static_cast<uint32_t>(
+            __builtin_amdgcn_update_dpp(static_cast<int>(v), static_cast<int>(v), 0x138, 0xF, 0xF, false));
 }
 __device__ __forceinline__ float rdlane_f(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
-__device__ __forceinline__ float wave_min_f(float v) {
-    v = row_ext_f<false>(v);
-    return fminf(fminf(rdlane_f(v, 0), rdlane_f(v, 16)), fminf(rdlane_f(v, 32), rdlane_f(v, 48)));
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-    v = row_ext_f<true>(v);
-    return fmaxf(fmaxf(rdlane_f(v, 0), rdlane_f(v, 16)), fmaxf(rdlane_f(v, 32), rdlane_f(v, 48)));
-}
-// min / max over lanes 0-15 (DPP within row 0), read from lane 0
-__device__ __forceinline__ float row0_min_f(float v) { return rdlane_f(row_ext_f<false>(v), 0); }
-__device__ __forceinline__ float row0_max_f(float v) { return rdlane_f(row_ext_f<true>(v), 0); }
 
 // Distance of p to the box [lo, hi] with the metric's own operation order;
 // every operand is <= the corresponding one of dist_metric(p, q) for any q in
@@ -359,33 +310,76 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
             if constexpr (MODE == 1) row = dense_w > 0 ? static_cast<int64_t>(qid) * dense_w : rs[qid];
         }
         // 1. All groups of the chunk first (a group = the lanes with identical
-        //    nine bins): every lane learns its group, whether it leads it (its
-        //    lowest lane) and its qsh slot, in (group, slot) order; lane G of
-        //    vgrp describes group G.
-        uint64_t todo = __builtin_amdgcn_ballot_w64(valid);
-        int ngrp = 0;
-        uint32_t goff = 0;   // queries in the groups so far
-        uint32_t mytag = 0;  // my group (bits 0-7), leader (bit 8), valid (bit 9), qsh slot (bits 16-23)
-        int vgrp = 0;        // lane G: size of group G (bits 0-7), its first slot (8-15), leader lane (16-23)
-        while (todo) {
-            const int leader = __builtin_ctzll(todo);
-            bool same = valid;
+        //    nine bins): every lane learns its group and whether it leads it
+        //    (its lowest lane); lane G of vgrp describes group G.
+        //    The query order puts equal lists next to each other, so a valid
+        //    lane leads a run of equal lists when it is lane 0 or a bin differs
+        //    from its left neighbour's (one DPP compare per bin, one ballot).
+        //    The runs are the groups, and a query's qsh slot is its lane, unless
+        //    two runs of the chunk have the same list (class-2 queries of
+        //    several voxels, wrapped Morton cells, the Linf rulebook search):
+        //    every leader writes its lane into a slot table under a hash of
+        //    its list and reads it back, and a leader that finds another lane
+        //    there sends the chunk through the compare loop, which merges such
+        //    runs.  Either way the groups are the sets of lanes with equal
+        //    lists, in the order of their lowest lanes.  The invalid lanes
+        //    (the tail of the last chunk) join no group.
+        bool lead = lane == 0;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) same = same && qb.b[k] == rdlane(static_cast<int>(qb.b[k]), leader);
-            const uint64_t gm = __builtin_amdgcn_ballot_w64(same);
-            todo &= ~gm;
-            const uint32_t ng = static_cast<uint32_t>(__popcll(gm));
-            if (same) {
-                const uint32_t slot = mbcnt64(gm);
-                mytag = static_cast<uint32_t>(ngrp) | (slot == 0 ? 0x300u : 0x200u) | ((goff + slot) << 16);
-            }
-            if (lane == ngrp) vgrp = static_cast<int>(ng | (goff << 8) | (static_cast<uint32_t>(leader) << 16));
-            goff += ng;
-            ++ngrp;
-        }
+        for (int k = 0; k < 9; ++k) lead |= qb.b[k] != left_lane(qb.b[k]);
+        lead &= valid;
+        const uint64_t lm = __builtin_amdgcn_ballot_w64(lead);
+        uint32_t hs = qb.b[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) hs += qb.b[k] << k;
+        hs = kRunSlot0 + ((hs ^ (hs >> 9)) & (kRunSlots - 1u));
+        int ngrp = __popcll(lm);
+        // my group (bits 0-7), leader (bit 8), valid (bit 9), qsh slot (bits 16-23)
+        uint32_t mytag = valid ? mbcnt64(lm) + (lead ? 0x300u : 0x1ffu) + (static_cast<uint32_t>(lane) << 16) : 0u;
         uint32_t* const tab = reinterpret_cast<uint32_t*>(cand);
-        // 2. The queries into qsh, once per chunk
         __syncthreads();  // previous chunk done with qsh / cand
+        // the leaders' lanes in group order and in the slot table (the
+        // candidate list is free until the first batch pass)
+        if (lead) {
+            tab[mytag & 0xffu] = static_cast<uint32_t>(lane);
+            tab[hs] = static_cast<uint32_t>(lane);
+        }
+        __syncthreads();
+        // lane G: size of group G (bits 0-7), its first slot (8-15), leader
+        // lane (16-23)
+        int vgrp = 0;
+        if (__builtin_amdgcn_ballot_w64(lead && tab[hs] != static_cast<uint32_t>(lane)) == 0) {
+            // a group ends where the next one starts
+            const uint32_t nvalid = static_cast<uint32_t>(__popcll(__builtin_amdgcn_ballot_w64(valid)));
+            if (lane < ngrp) {
+                const uint32_t l0 = tab[lane];
+                const uint32_t l1 = lane + 1 < ngrp ? tab[lane + 1] : nvalid;
+                vgrp = static_cast<int>((l1 - l0) | (l0 << 8) | (l0 << 16));
+            }
+        } else {
+            uint64_t todo = __builtin_amdgcn_ballot_w64(valid);
+            uint32_t goff = 0;  // queries in the groups so far
+            ngrp = 0;
+            while (todo) {
+                const int leader = __builtin_ctzll(todo);
+                bool same = valid;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) same = same && qb.b[k] == rdlane(static_cast<int>(qb.b[k]), leader);
+                const uint64_t gm = __builtin_amdgcn_ballot_w64(same);
+                todo &= ~gm;
+                const uint32_t ng = static_cast<uint32_t>(__popcll(gm));
+                if (same) {
+                    const uint32_t slot = mbcnt64(gm);
+                    mytag = static_cast<uint32_t>(ngrp) | (slot == 0 ? 0x300u : 0x200u) | ((goff + slot) << 16);
+                }
+                if (lane == ngrp) vgrp = static_cast<int>(ng | (goff << 8) | (static_cast<uint32_t>(leader) << 16));
+                goff += ng;
+                ++ngrp;
+            }
+        }
+        // vsplit, lane G: the lane split of group G's size (one vector load per chunk)
+        const int vsplit = static_cast<int>(kLaneSplit[vgrp & 0xff]);
+        // 2. The queries into qsh, once per chunk
         if (valid) {
             qsh[mytag >> 16] = q4;
             if constexpr (MODE == 1) qrow[mytag >> 16] = row;
@@ -396,6 +390,7 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
         //    and bit 9 t + k of km says that visited bin k of the batch's t-th
         //    group is a live segment.
         uint32_t vst = 0, vlen = 0;
+        float vbox = 0.f;  // lane 8 t + d: word d of the box of the batch's t-th group (min x, y, z, max x, y, z)
         uint64_t km = 0;
         int gi = 0, nbat = 0;  // group within the batch, groups of the batch
         for (int grp = 0; grp < ngrp; ++grp, ++gi) {
@@ -451,6 +446,14 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
                 const uint32_t prev = tq[5 + tk];  // the bin before mine (tk > 0)
                 const uint4 b0 = reinterpret_cast<const uint4*>(tq)[0];
                 const uint2 b1 = reinterpret_cast<const uint2*>(tq)[2];
+                // The batch's boxes in one lane table for the group loop: lane
+                // 8 t + d takes word d of group t's box (tab ends at byte 448,
+                // seg starts at 512).  The integer min / max of the keys is
+                // exact, so this is the box a float min / max over the members
+                // gives, up to the sign of a zero (-0 keys below +0); box_dist
+                // squares the gap or takes its magnitude, so the sign of a zero
+                // edge does not change which points pass.
+                vbox = __uint_as_float(key_float(static_cast<int32_t>(tab[16 * (bl >> 3) + (bl & 7)])));
                 // the bin's bounds and its class directory entry in flight together
                 // (the directory exists for every bin when `sub`): no load under a
                 // lane condition
@@ -505,25 +508,21 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
             const uint32_t gslot = (ginfo >> 8) & 0xffu, leader = ginfo >> 16;
             // a group shares its buckets, hence its batch item
             const uint32_t gbase = REL16 ? rdlane(static_cast<int>(pbase), leader) : 0u;
-            // group bounding box over the member slots qsh[gslot, gslot + ng): groups
-            // of <= 16 (nearly all) within one 16-lane DPP row, larger ones the whole wave
-            float lx, ly, lz, hx, hy, hz;
-            if (ng <= 16) {
-                const float4 v = lane < ng ? qsh[gslot + (lane & 15)] : far;
-                const float4 w = lane < ng ? v : make_float4(-inf, -inf, -inf, 0.f);
-                lx = row0_min_f(v.x), ly = row0_min_f(v.y), lz = row0_min_f(v.z);
-                hx = row0_max_f(w.x), hy = row0_max_f(w.y), hz = row0_max_f(w.z);
-            } else {
-                const float4 v = lane < ng ? qsh[gslot + lane] : far;
-                const float4 w = lane < ng ? v : make_float4(-inf, -inf, -inf, 0.f);
-                lx = wave_min_f(v.x), ly = wave_min_f(v.y), lz = wave_min_f(v.z);
-                hx = wave_max_f(w.x), hy = wave_max_f(w.y), hz = wave_max_f(w.z);
-            }
+            // group bounding box over the member slots qsh[gslot, gslot + ng),
+            // reduced by the batch pass
+            const float lx = rdlane_f(vbox, 8 * gi), ly = rdlane_f(vbox, 8 * gi + 1),
+                        lz = rdlane_f(vbox, 8 * gi + 2);
+            float hx = rdlane_f(vbox, 8 * gi + 3), hy = rdlane_f(vbox, 8 * gi + 4),
+                  hz = rdlane_f(vbox, 8 * gi + 5);
+            // the upper corner pinned in VGPRs: the filter's v_med3 takes one
+            // scalar operand, and a second one would be moved to a VGPR again
+            // in every round of the stream loop
+            asm volatile("" : "+v"(hx), "+v"(hy), "+v"(hz));
             // lane -> (query g, slice s)
             // S = floor(64 / ng) lanes per query (not a power of two: 9 queries
             // take 63 lanes, not 9 of 16 slots x 4); g = lane / S by the
             // multiply-shift of the table, exact for lane < 64
-            const uint32_t split = kLaneSplit[ng];
+            const uint32_t split = rdlane(vsplit, static_cast<uint32_t>(grp));
             const int S = static_cast<int>(split & 0xffu);
             const int g = static_cast<int>((static_cast<uint32_t>(lane) * (split >> 8)) >> 16);
             const int sl = lane - g * S;
