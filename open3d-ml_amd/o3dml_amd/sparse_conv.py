@@ -323,11 +323,22 @@ class _RulebookScope:
         True when all were lattice sets (their maps are valid)."""
         if not self.pending:
             return True
-        st = torch.cat(self.pending).cpu()
+        status = torch.cat(self.pending)
         self.pending.clear()
-        if bool((st & 1).any()):
-            raise RuntimeError("sparse_conv: two neighbours of one output share a kernel index")
-        return not bool((st & 4).any())
+        return lattice_status_ok(status)
+
+
+def lattice_status_ok(status):
+    """Reads the concatenated lattice status words of a scope or of a captured
+    body (None: there were none) back to the host: True when every map was a
+    lattice map, False when the caller must recompute with the search
+    rulebook; duplicate kernel indices raise."""
+    if status is None:
+        return True
+    st = status.cpu()
+    if bool((st & 1).any()):
+        raise RuntimeError("sparse_conv: two neighbours of one output share a kernel index")
+    return not bool((st & 4).any())
 
 
 _SCOPE = None  # the active rulebook_cache() scope
@@ -340,29 +351,10 @@ def active_scope():
 
 def note_search_rulebook():
     """A layer built its rulebook with the fixed-radius search (not the lattice
-    map): counted in the active scope (sparseconvnet._ScnHead / _ScnTail then do not
+    map): counted in the active scope (sparseconvnet._capture_body then does not
     capture the body: the search reads sizes back to the host)."""
     if _SCOPE is not None:
         _SCOPE.searches += 1
-
-
-@contextlib.contextmanager
-def rulebook_scope(scope):
-    """Make an existing _RulebookScope the active one (a graph captured in
-    parts continues one scope: the later part finds the earlier part's maps)."""
-    global _SCOPE
-    prev, _SCOPE = _SCOPE, scope
-    try:
-        yield scope
-    finally:
-        _SCOPE = prev
-
-
-def scope_from(maps, defer_checks=True):
-    """A fresh scope that starts with the given kernel maps."""
-    sc_ = _RulebookScope(defer_checks)
-    sc_.maps = dict(maps)
-    return sc_
 
 
 @contextlib.contextmanager

@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import ops
 from . import sparse_conv as sc
 from .layers import SparseConv, SparseConvTranspose
-from .sparse_conv import rulebook_cache, rulebook_scope, scope_from
+from .sparse_conv import rulebook_cache
 
 
 class BatchNormBlock(nn.Module):
@@ -148,7 +148,7 @@ class Convolution(nn.Module):
                               offset=torch.full((3,), offset, dtype=torch.float32), normalize=normalize)
 
     def forward(self, features_list, in_positions_list, voxel_size=1.0, out_positions_list=None):
-        if out_positions_list is None:  # UNet passes the grids it computed on its side stream
+        if out_positions_list is None:  # UNet passes the grids computed up front (_level_grids)
             out_positions_list = [ops.calculate_grid(p) for p in in_positions_list]
         out_feat = [self.net(f, i, o, voxel_size) for f, i, o in zip(features_list, in_positions_list,
                                                                     out_positions_list)]
@@ -248,89 +248,55 @@ def _unet_layers(planes, residual, reps):
     return layers
 
 
-def _grid_mode():
-    """O3DML_SCN_GRIDS: "front" (default) computes every level's grid before
-    the first convolution is queued, "side" computes each when its
-    Convolution needs it on a side stream (A/B)."""
-    import os
-    return os.environ.get("O3DML_SCN_GRIDS", "front")
-
-
-class _LevelGrids:
-    """The stride-2 grid of each level (calculate_grid, then / 2) for the
-    UNet's Convolutions.  calculate_grid reads its output size back to the
-    host; issued on the caller's stream between the convolutions, that read
-    waited for every convolution queued above it.  "front": all levels are
-    computed when this object is made (before any convolution: the reads wait
-    only for the grid kernels).  "side": each level when its Convolution needs
-    it, on a side stream, so the read waits only for the grid kernels while
-    the queued convolutions keep the GPU busy; the side stream first waits for
-    the caller's stream as of construction (the input positions), each grid
-    (the next level's input) is then ordered on the side stream itself, and
-    the caller's stream waits for the side stream before it uses a grid."""
-    _streams = {}
-
-    def __init__(self, pos_list, n_down):
-        self.dev = pos_list[0].device if pos_list and pos_list[0].is_cuda else None
-        self.ready = None
-        self.chain = None
-        if _grid_mode() != "side" or self.dev is None:
-            self.chain = []
-            for _ in range(n_down):
-                outs = [ops.calculate_grid(p) for p in pos_list]
-                pos_list = [o / 2 for o in outs]
-                self.chain.append((outs, pos_list))
-            self.chain.reverse()
-        else:
-            self.main = torch.cuda.current_stream(self.dev)
-            self.ready = torch.cuda.Event()
-            self.ready.record(self.main)
-
-    def next(self, pos_list):
-        if self.chain is not None:
-            return self.chain.pop()
-        side = self._streams.get(self.dev)
-        if side is None:
-            side = self._streams[self.dev] = torch.cuda.Stream(self.dev)
-        if self.ready is not None:
-            side.wait_event(self.ready)
-            self.ready = None
-        with torch.cuda.stream(side):
-            outs = [ops.calculate_grid(p) for p in pos_list]
-            half = [o / 2 for o in outs]
-        for t in outs + half:
-            t.record_stream(self.main)  # freed blocks wait for the caller's stream
-        self.main.wait_stream(side)
-        return outs, half
+def _level_grids(pos_list, n_down):
+    """The stride-2 grid of each level (calculate_grid) and the next level's
+    positions (grid / 2) for the UNet's Convolutions, all computed here,
+    before any convolution is queued: calculate_grid reads its output size
+    back to the host, and issued between the convolutions that read waited
+    for every convolution queued above it."""
+    outs_per_level, halves_per_level = [], []
+    for _ in range(n_down):
+        outs = [ops.calculate_grid(p) for p in pos_list]
+        pos_list = [o / 2 for o in outs]
+        outs_per_level.append(outs)
+        halves_per_level.append(pos_list)
+    return outs_per_level, halves_per_level
 
 
 class _FixedGrids:
-    """_LevelGrids' interface over the per-level grids of a captured body:
-    level l's Convolution output grid, the next level's positions = grid / 2
-    computed in the body (one kernel, no extra graph input) unless given
-    (halves_per_level: the plan's, same bits)."""
+    """The per-level grids a UNet forward consumes, one level per Convolution:
+    level l's output grid and the next level's positions = grid / 2, computed
+    here (in a captured body: one kernel, no extra graph input) unless given
+    (halves_per_level: _level_grids' or the plan's, same bits)."""
 
     def __init__(self, outs_per_level, halves_per_level=None):
         self.levels = list(outs_per_level)
         self.halves = None if halves_per_level is None else list(halves_per_level)
 
-    def next(self, pos_list):
+    def next(self):
         outs = self.levels.pop(0)
         if self.halves is not None:
             return outs, self.halves.pop(0)
         return outs, [o / 2 for o in outs]
 
 
+_GRAPH_MODES = ("0", "1", "3")
+
+
 def _graph_mode():
-    """O3DML_SCN_GRAPH: "1" replays the eval body as ONE HIP graph per size
-    signature (_ScnBody), "2" as a head + tail pair with the deeper
-    level grids computed on a side stream while the head replays
-    (_ScnHead / _ScnTail), "3" runs the InputLayer and every level grid as
-    one library call into persistent buffers the captured body reads in
-    place (_ScnPlan / _ScnPlanBody; the default), "0" runs it eagerly (A/B).
+    """O3DML_SCN_GRAPH, how an eval forward without autograd runs its body:
+    "3" (the default) runs the InputLayer and every level grid as one library
+    call into persistent buffers the captured body reads in place (_ScnPlan /
+    _ScnPlanBody); "1" runs the InputLayer and the level grids eagerly and
+    replays the body as one HIP graph per size signature (_ScnBody) — also
+    what mode 3 falls back to for batched input and for tensors the plan does
+    not take; "0" runs everything eagerly (A/B, the tests' reference).
     Modes 1 and 3 capture a signature the second time it is seen
-    (SparseConvUnet._seen_before)."""
-    return os.environ.get("O3DML_SCN_GRAPH", "3")
+    (SparseConvUnet._seen_before).  Any other value raises."""
+    mode = os.environ.get("O3DML_SCN_GRAPH", "3")
+    if mode not in _GRAPH_MODES:
+        raise ValueError(f"O3DML_SCN_GRAPH={mode!r}: expected one of \"0\", \"1\", \"3\"")
+    return mode
 
 
 def _map_stream_on():
@@ -347,12 +313,6 @@ def _map_stream(dev):
     if s is None:
         s = _MAP_STREAMS[dev] = torch.cuda.Stream(dev)
     return s
-
-
-def _copy_into(dst_lists, src_lists):
-    for dl, sl in zip(dst_lists, src_lists):
-        for dst, src in zip(dl, sl):
-            dst.copy_(src)
 
 
 class _ScnPlan:
@@ -389,31 +349,41 @@ class _ScnPlan:
         return n, self.vpos[:nv], self.vfeat[:nv], self.imap[:n], (outs, halves)
 
 
+def _capture_body(dev, body):
+    """Captures body() as a HIP graph: (graph, its output, its concatenated
+    lattice status words or None).  The body first runs once on a fresh side
+    stream (warm-up: lazy caches and library state stay outside the capture);
+    graph is None when that run was off the lattice or put a layer on the
+    search rulebook (e.g. an empty level; it reads sizes back to the host):
+    the caller takes the eager path."""
+    main = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        with rulebook_cache(defer_checks=True) as scope:
+            body()
+            ok = scope.check()
+            searches = scope.searches
+    main.wait_stream(side)
+    if not ok or searches:
+        return None, None, None
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        with rulebook_cache(defer_checks=True) as scope:
+            out = body()
+            status = torch.cat(scope.pending) if scope.pending else None
+            scope.pending.clear()
+    return graph, out, status
+
+
 class _ScnPlanBody:
     """The eval body (every convolution and map, the head, the OutputLayer
     gather) captured per size signature on a _ScnPlan's buffers and replayed
     per frame right after the one-call plan — no input copies."""
 
     def __init__(self, model, pos, feat, imap, grids):
-        dev = pos.device
-        main = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):  # warm-up: lazy caches and library state outside the capture
-            with rulebook_cache(defer_checks=True) as scope:
-                model._plan_body(pos, feat, imap, grids)
-                ok = scope.check()
-                searches = scope.searches
-        main.wait_stream(side)
-        self.graph = None
-        if not ok or searches:
-            return
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            with rulebook_cache(defer_checks=True) as scope:
-                self.out = model._plan_body(pos, feat, imap, grids)
-                self.status = torch.cat(scope.pending) if scope.pending else None
-                scope.pending.clear()
+        self.graph, self.out, self.status = _capture_body(
+            pos.device, lambda: model._plan_body(pos, feat, imap, grids))
 
 
 class _ScnBody:
@@ -432,27 +402,9 @@ class _ScnBody:
         self.pos = [p.clone() for p in pos_list]
         self.feat = [f.clone() for f in feat_list]
         self.outs = [[o.clone() for o in outs] for outs in outs_per_level]
-        main = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):  # warm-up: lazy caches and library state outside the capture
-            with rulebook_cache(defer_checks=True) as scope:
-                model._body(self.pos, self.feat, _FixedGrids(self.outs))
-                ok = scope.check()
-                searches = scope.searches
-        main.wait_stream(side)
-        self.lattice = ok
-        self.graph = None
-        # off-lattice input, or a layer on the search rulebook (e.g. an empty
-        # level): the caller takes the eager path
-        if not ok or searches:
-            return
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            with rulebook_cache(defer_checks=True) as scope:
-                self.out = model._body(self.pos, self.feat, _FixedGrids(self.outs))
-                self.status = torch.cat(scope.pending) if scope.pending else None
-                scope.pending.clear()
+        # no halves: the body computes them from its static grids
+        self.graph, self.out, self.status = _capture_body(
+            dev, lambda: model._body(self.pos, self.feat, _FixedGrids(self.outs)))
 
     def run(self, pos_list, feat_list, outs_per_level):
         """Replay on this frame's inputs; None when a level is off the lattice."""
@@ -464,123 +416,7 @@ class _ScnBody:
             for dst, src in zip(dl, sl):
                 dst.copy_(src)
         self.graph.replay()
-        if self.status is not None:
-            st = self.status.cpu()
-            if bool((st & 1).any()):
-                raise RuntimeError("sparse_conv: two neighbours of one output share a kernel index")
-            if bool((st & 4).any()):
-                return None
-        return self.out
-
-
-class _ScnTail:
-    """The eval body from the second Convolution on (needs level grids 1..),
-    captured per grid-size signature under one _ScnHead, continuing the
-    head's rulebook scope (the level-0 map the decoder's last block reuses is
-    the head's); its graph also concatenates every lattice status word."""
-
-    def __init__(self, model, head, rest):
-        dev = head.pos[0].device
-        self.outs = [[o.clone() for o in outs] for outs in rest]
-        main = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):  # warm-up on the head's outputs of this frame, in a scratch scope
-            import copy
-            with rulebook_scope(scope_from(head.maps)) as scope:
-                model._body_tail(copy.copy(head.state), _FixedGrids(self.outs), fresh=True)
-                scope.pending[:0] = head.pending
-                ok = scope.check()
-                searches = scope.searches
-        main.wait_stream(side)
-        self.graph = None
-        if not ok or searches:  # off-lattice, or a layer on the search rulebook: eager path
-            return
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            with rulebook_scope(scope_from(head.maps)) as scope:
-                self.out = model._body_tail(copy.copy(head.state), _FixedGrids(self.outs), fresh=True)
-                pending = head.pending + scope.pending
-                self.status = torch.cat(pending) if pending else None
-
-
-class _ScnHead:
-    """The eval body up to the second Convolution — the input convolution,
-    the level-0 block, the first stride-2 Convolution (level-0 grid) and the
-    level-1 block — captured once per (voxels, level-0 grid points) as a HIP
-    graph.  Its replay runs while the host computes the deeper level grids
-    on a side stream (each calculate_grid reads its size back: those reads
-    then wait only for the grid kernels, not for the convolutions); the tail
-    (_ScnTail, per deeper grid sizes) replays after them.  Inputs are copied
-    into the graphs' static buffers; the lattice status words are read once
-    per frame, after the tail (the eager path's scope.check)."""
-
-    _MAX_TAILS = 4
-
-    def __init__(self, model, pos_list, feat_list, outs0, rest):
-        dev = pos_list[0].device
-        self.pos = [p.clone() for p in pos_list]
-        self.feat = [f.clone() for f in feat_list]
-        self.outs0 = [[o.clone() for o in outs0]]
-        self.tails = {}
-        main = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):  # warm-up of the whole body: lazy caches and library state
-            with rulebook_cache(defer_checks=True) as scope:
-                st = model._body_head(self.pos, self.feat, self.outs0)
-                model._body_tail(st, _FixedGrids([[o.clone() for o in outs] for outs in rest]))
-                ok = scope.check()
-                searches = scope.searches
-        main.wait_stream(side)
-        self.graph = None
-        if not ok or searches:
-            return
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            with rulebook_cache(defer_checks=True) as scope:
-                self.state = model._body_head(self.pos, self.feat, self.outs0)
-                self.maps = dict(scope.maps)
-                self.pending = list(scope.pending)
-
-    def replay(self, pos_list, feat_list, outs0):
-        _copy_into([self.pos, self.feat], [pos_list, feat_list])
-        _copy_into(self.outs0, [outs0])
-        self.graph.replay()
-
-    def tail(self, model, rest):
-        key = tuple(tuple(int(o.shape[0]) for o in outs) for outs in rest)
-        t = self.tails.pop(key, None)
-        if t is None:
-            t = _ScnTail(model, self, rest)
-            while len(self.tails) >= self._MAX_TAILS:
-                self.tails.pop(next(iter(self.tails)))
-        self.tails[key] = t
-        return t
-
-
-_GRID_STREAMS = {}
-
-
-def _grid_stream(dev):
-    """One side stream per device for the deeper level grids (created once;
-    O3DML_SCN_SIDE_PRIO=1: at the highest stream priority, A/B)."""
-    st = _GRID_STREAMS.get(str(dev))
-    if st is None:
-        prio = 0
-        if os.environ.get("O3DML_SCN_SIDE_PRIO", "0") == "1":
-            prio = torch.cuda.Stream.priority_range()[1]
-        st = _GRID_STREAMS[str(dev)] = torch.cuda.Stream(dev, priority=prio)
-    return st
-
-
-def _status_ok(status):
-    if status is None:
-        return True
-    st = status.cpu()
-    if bool((st & 1).any()):
-        raise RuntimeError("sparse_conv: two neighbours of one output share a kernel index")
-    return not bool((st & 4).any())
+        return self.out if sc.lattice_status_ok(self.status) else None
 
 
 class UNet(nn.Module):
@@ -593,24 +429,6 @@ class UNet(nn.Module):
 
     def n_down(self):
         return sum(isinstance(m, Convolution) for m in self.net)
-
-    def split_index(self, k):
-        """Index in self.net of the k-th Convolution (1-based; len(net) if
-        there are fewer): a run stopped there needs only the first k - 1
-        level grids."""
-        seen = 0
-        for j, m in enumerate(self.net):
-            if isinstance(m, Convolution):
-                seen += 1
-                if seen == k:
-                    return j
-        return len(self.net)
-
-    def begin(self, pos_list, feat_list):
-        """State of a (resumable) forward: run(state, grids, stop) advances it."""
-        import types
-        return types.SimpleNamespace(j=0, pos_list=pos_list, feat_list=feat_list, conv_pos=[], conv_out=[],
-                                     concat_feat=[], pre=None)
 
     def map_schedule(self, pos, outs, halves):
         """The (layer, input positions, output positions) of every kernel map
@@ -636,24 +454,16 @@ class UNet(nn.Module):
 
     def forward(self, pos_list, feat_list, grids=None):
         if grids is None:
-            grids = _LevelGrids(pos_list, self.n_down())
-        st = self.begin(pos_list, feat_list)
-        self.run(st, grids)
-        return st.feat_list
-
-    def run(self, st, grids, stop=None):
+            grids = _FixedGrids(*_level_grids(pos_list, self.n_down()))
         # conv_out: each Convolution's output grid in the fine level's units —
         # the DeConvolution's input positions (= 2 x the coarse positions,
         # exactly), the same tensor, so the DeConvolution's kernel map is
         # derived from the Convolution's (sparse_conv._transpose_of_cached)
         mods = list(self.net)
-        stop = len(mods) if stop is None else stop
         fuse = _fusable(self)
-        conv_pos, conv_out, concat_feat = st.conv_pos, st.conv_out, st.concat_feat
-        pos_list, feat_list, pre = st.pos_list, st.feat_list, st.pre
-        # pending folded BN + ReLU (eval): applied by the next conv's gather
-        for j in range(st.j, stop):
-            m = mods[j]
+        conv_pos, conv_out, concat_feat = [], [], []
+        pre = None  # pending folded BN + ReLU (eval): applied by the next conv's gather
+        for j, m in enumerate(mods):
             if fuse and isinstance(m, BatchNormBlock) and j + 2 < len(mods) and \
                     isinstance(mods[j + 1], ReLUBlock) and \
                     isinstance(mods[j + 2], (SubmanifoldSparseConv, Convolution, DeConvolution)):
@@ -666,7 +476,7 @@ class UNet(nn.Module):
                     feat_list = [m.net.forward_fused(f, p, p, 1.0, pre=pre) for f, p in zip(feat_list, pos_list)]
                 elif isinstance(m, Convolution):
                     conv_pos.append(pos_list)
-                    outs, half = grids.next(pos_list)
+                    outs, half = grids.next()
                     conv_out.append(outs)
                     feat_list = [m.net.forward_fused(f, p, o, 1.0, pre=pre)
                                  for f, p, o in zip(feat_list, pos_list, outs)]
@@ -683,7 +493,7 @@ class UNet(nn.Module):
                 feat_list = m(feat_list, pos_list)
             elif isinstance(m, Convolution):
                 conv_pos.append(pos_list)
-                outs, half = grids.next(pos_list)
+                outs, half = grids.next()
                 conv_out.append(outs)
                 feat_list, _ = m(feat_list, pos_list, out_positions_list=outs)
                 pos_list = half
@@ -696,8 +506,7 @@ class UNet(nn.Module):
                 feat_list = m(concat_feat.pop(), feat_list)
             else:
                 raise Exception("Unknown module {}".format(m))
-        st.j, st.pos_list, st.feat_list, st.pre = stop, pos_list, feat_list, pre
-        return st
+        return feat_list
 
 
 class SparseConvUnet(nn.Module):
@@ -724,10 +533,7 @@ class SparseConvUnet(nn.Module):
         mode = _graph_mode()
         if mode != "0" and not self.training and not torch.is_grad_enabled() and len(inputs.point) and \
                 inputs.point[0].is_cuda:
-            if mode == "3":
-                out = self._forward_plan(inputs)
-            else:
-                out = self._forward_graph(inputs) if mode == "2" else self._forward_graph_single(inputs)
+            out = self._forward_plan(inputs) if mode == "3" else self._forward_graph_single(inputs)
             if out is not None:
                 return out
         # lattice checks of all levels are read back once at the end; a
@@ -772,20 +578,6 @@ class SparseConvUnet(nn.Module):
         feat_list = self.relu(self.batch_norm(feat_list))
         return self.output_layer(self.linear(feat_list), index_maps)
 
-    def _body_head(self, pos_list, feat_list, outs0):
-        """The body up to the second Convolution (needs the level-0 grid only)."""
-        feat_list = self.sub_sparse_conv(feat_list, pos_list, voxel_size=1.0)
-        st = self.unet.begin(pos_list, feat_list)
-        return self.unet.run(st, _FixedGrids(outs0), stop=self.unet.split_index(2))
-
-    def _body_tail(self, st, grids, fresh=False):
-        """The rest of the body from a _body_head state.  fresh: st is a
-        shallow copy whose lists must not be shared with the head's."""
-        if fresh:
-            st.conv_pos, st.conv_out, st.concat_feat = list(st.conv_pos), list(st.conv_out), list(st.concat_feat)
-        self.unet.run(st, grids)
-        return st.feat_list
-
     def _param_key(self):
         """(address, version) of every parameter and buffer: a captured body
         is only replayed on the weights it was captured with.  The tensor list
@@ -828,8 +620,7 @@ class SparseConvUnet(nn.Module):
         """Drop the kept tensor list and everything captured on the tensors it
         names (graph bodies, the sightings) and, unless keep_plan (it holds no
         weights, only input buffers on the model's device), the plan."""
-        for name in ("_o3dml_state_tensors", "_o3dml_scn_bodies", "_o3dml_scn_single", "_o3dml_scn_plan_bodies",
-                     "_o3dml_scn_seen"):
+        for name in ("_o3dml_state_tensors", "_o3dml_scn_single", "_o3dml_scn_plan_bodies", "_o3dml_scn_seen"):
             self.__dict__.pop(name, None)
         if not keep_plan:
             self.__dict__.pop("_o3dml_scn_plan", None)
@@ -844,64 +635,6 @@ class SparseConvUnet(nn.Module):
             return super().load_state_dict(*args, **kwargs)
         finally:
             self._invalidate_eval_caches()
-
-    def _forward_graph(self, inputs):
-        """Eval forward with the body replayed from captured graphs (_ScnHead /
-        _ScnTail): the InputLayer and the level-0 grid run eagerly, the head
-        replays while the deeper grids are computed on a side stream, then the
-        tail.  None when the input is off the voxel lattice (the caller
-        recomputes eagerly)."""
-        pos_list, feat_list, index_maps = self._inputs(inputs)
-        n_down = self.unet.n_down()
-        if n_down < 2:
-            return None
-        outs0 = [ops.calculate_grid(x) for x in pos_list]
-        dev = pos_list[0].device
-        key = (str(dev), tuple(int(x.shape[0]) for x in pos_list), tuple(int(o.shape[0]) for o in outs0),
-               self._param_key())
-        heads = self.__dict__.setdefault("_o3dml_scn_bodies", {})
-        head = heads.pop(key, None)
-        fresh = head is None
-
-        def deeper(outs):
-            rest, p = [], [o / 2 for o in outs]
-            for _ in range(n_down - 1):
-                o = [ops.calculate_grid(x) for x in p]
-                rest.append(o)
-                p = [x / 2 for x in o]
-            return rest
-
-        if fresh:  # first frame of this signature: grids first, then the captures
-            rest = deeper(outs0)
-            head = _ScnHead(self, pos_list, feat_list, outs0, rest)
-            while len(heads) >= self._MAX_GRAPHS:
-                heads.pop(next(iter(heads)))
-        heads[key] = head
-        if head.graph is None:
-            return None
-        main = torch.cuda.current_stream(dev)
-        grids_in = torch.cuda.Event()
-        grids_in.record(main)  # the level-0 grid is ready (before the head's replay is queued)
-        head.replay(pos_list, feat_list, outs0)
-        if not fresh:
-            # the deeper grids on a side stream while the head replays: each
-            # size read waits only for the grid kernels
-            side = _grid_stream(dev)
-            side.wait_event(grids_in)
-            with torch.cuda.stream(side):
-                rest = deeper(outs0)
-            for outs in rest:
-                for t in outs:
-                    t.record_stream(main)
-            main.wait_stream(side)
-        tail = head.tail(self, rest)
-        if tail.graph is None:
-            return None
-        _copy_into(tail.outs, rest)
-        tail.graph.replay()
-        if not _status_ok(tail.status):
-            return None
-        return self._head(tail.out, index_maps)
 
     def _plan_body(self, pos, feat, imap, grids):
         """The eval body on the plan's buffers.  With O3DML_SCN_MAP_STREAM (default
@@ -978,7 +711,7 @@ class SparseConvUnet(nn.Module):
         if body.graph is None:
             return None
         body.graph.replay()
-        if not _status_ok(body.status):
+        if not sc.lattice_status_ok(body.status):
             return None
         return body.out.clone()
 
@@ -988,11 +721,7 @@ class SparseConvUnet(nn.Module):
         eagerly, then the body of their size signature replays.  None when the
         input is off the voxel lattice (the caller recomputes eagerly)."""
         pos_list, feat_list, index_maps = self._inputs(inputs)
-        outs_per_level, p = [], pos_list
-        for _ in range(self.unet.n_down()):
-            outs = [ops.calculate_grid(x) for x in p]
-            outs_per_level.append(outs)
-            p = [o / 2 for o in outs]
+        outs_per_level, halves_per_level = _level_grids(pos_list, self.unet.n_down())
         key = (str(pos_list[0].device), tuple(int(x.shape[0]) for x in pos_list),
                tuple(tuple(int(o.shape[0]) for o in outs) for outs in outs_per_level), self._param_key())
         bodies = self.__dict__.setdefault("_o3dml_scn_single", {})
@@ -1000,7 +729,7 @@ class SparseConvUnet(nn.Module):
         if body is None:
             if not self._seen_before(("single",) + key):  # first sighting: eagerly
                 with rulebook_cache(defer_checks=True) as scope:
-                    out = self._body(pos_list, feat_list, _FixedGrids(outs_per_level))
+                    out = self._body(pos_list, feat_list, _FixedGrids(outs_per_level, halves_per_level))
                     if not scope.check():
                         return None
                 return self._head(out, index_maps)
@@ -1016,13 +745,6 @@ class SparseConvUnet(nn.Module):
         return self._head(out, index_maps)
 
     def _forward(self, inputs):
-        pos_list, feat_list, index_maps = [], [], []
-        for i in range(len(inputs.batch_lengths)):
-            f, p, m = self.input_layer(inputs.feat[i], inputs.point[i])
-            pos_list.append(p)
-            feat_list.append(f)
-            index_maps.append(m)
-        grids = _LevelGrids(pos_list, self.unet.n_down())  # before the first convolution is queued
-        feat_list = self.sub_sparse_conv(feat_list, pos_list, voxel_size=1.0)
-        feat_list = self.unet(pos_list, feat_list, grids=grids)
-        return self._head(feat_list, index_maps)
+        pos_list, feat_list, index_maps = self._inputs(inputs)
+        grids = _FixedGrids(*_level_grids(pos_list, self.unet.n_down()))  # before the first convolution is queued
+        return self._head(self._body(pos_list, feat_list, grids), index_maps)

@@ -33,11 +33,13 @@ keeps it so: it asserts that no reference error exceeds 1e-2 and that at most
 full-gradient error above 5e-4 (here none; feature seed 11 gave 7 of 125 in
 train mode, first-layer kernel gradients 3e-3 .. 5e-3 off, and was replaced).
 
-The graph modes are also held to the eager forward bit for bit on room A (its
-level 0 runs the multi-workgroup plan levels), with feature rows wider than
-the three columns the InputLayer averages, and after parameters or buffers
-were replaced by other tensors (load_state_dict(assign=True), a new
-nn.Parameter, a fresh buffer at version 0)."""
+The graph modes (O3DML_SCN_GRAPH 1: one captured body per size signature; 3,
+the default: the one-call plan and a body captured on its buffers) are also
+held to the eager forward (mode 0) bit for bit on room A (its level 0 runs the
+multi-workgroup plan levels), with feature rows wider than the three columns
+the InputLayer averages, after parameters or buffers were replaced by other
+tensors (load_state_dict(assign=True), a new nn.Parameter, a fresh buffer at
+version 0), and on a batch of two, which mode 3 hands to mode 1's path."""
 import os
 import sys
 import types
@@ -159,17 +161,15 @@ def test_scn_fused_eval_matches_unfused(cuda, residual):
     assert err < 1e-5, err
 
 
-@pytest.mark.parametrize("mode", ["1", "2", "3", "3-inline-maps"])
+@pytest.mark.parametrize("mode", ["1", "3", "3-inline-maps"])
 @pytest.mark.parametrize("residual", [True, False])
 def test_scn_graph_replay_equals_eager(cuda, residual, mode, monkeypatch):
     """The eval body replayed from HIP graphs gives the eager forward's logits
     bit for bit — mode "1": one graph per size signature
-    (sparseconvnet._ScnBody); mode "2": _ScnHead up to the second Convolution,
-    replayed while the deeper level grids are computed on a side stream, then
-    _ScnTail per deeper grid sizes; mode "3": the InputLayer and every level
+    (sparseconvnet._ScnBody); mode "3": the InputLayer and every level
     grid as one library call (o3dml_scn_plan) into persistent buffers the
     captured body reads in place — on the first sighting of a size signature
-    (eager, nothing captured in modes 1 / 3), on the capture frame, on replays
+    (eager, nothing captured), on the capture frame, on replays
     with new features, after a second room (second signature) was captured in
     between, and after the weights change (a new capture keyed on the
     parameter versions).  Mode 3 builds the kernel maps on a second stream
@@ -177,7 +177,7 @@ def test_scn_graph_replay_equals_eager(cuda, residual, mode, monkeypatch):
     _graph_replay_equals_eager(cuda, residual, mode, monkeypatch, _inputs(cuda), (2, 3))
 
 
-@pytest.mark.parametrize("mode", ["1", "2", "3", "3-inline-maps"])
+@pytest.mark.parametrize("mode", ["1", "3", "3-inline-maps"])
 @pytest.mark.parametrize("residual", [True, False])
 def test_scn_graph_replay_equals_eager_room_a(cuda, residual, mode, monkeypatch):
     """test_scn_graph_replay_equals_eager on the training fixture's room A
@@ -212,10 +212,9 @@ def _graph_replay_equals_eager(cuda, residual, mode, monkeypatch, inp, part, abo
             assert int(m.__dict__["_o3dml_scn_plan"][1].sizes[0]) > above
         return out
 
-    name = {"1": "_o3dml_scn_single", "2": "_o3dml_scn_bodies", "3": "_o3dml_scn_plan_bodies"}[mode]
+    name = {"1": "_o3dml_scn_single", "3": "_o3dml_scn_plan_bodies"}[mode]
     assert torch.equal(run(inp, True), run(inp, False))
-    if mode != "2":  # captured on the second sighting of a size signature
-        assert len(m.__dict__.get(name, {})) == 0
+    assert len(m.__dict__.get(name, {})) == 0  # captured on the second sighting of a size signature
     frames = [types.SimpleNamespace(point=inp.point, feat=[torch.rand_like(inp.feat[0])], batch_lengths=[n]),
               room2, room2, inp]
     for x in frames:
@@ -224,9 +223,6 @@ def _graph_replay_equals_eager(cuda, residual, mode, monkeypatch, inp, part, abo
     assert len(cache) == 2 and all(b.graph is not None for b in cache.values())
     if mode == "3":
         assert all(isinstance(b, S._ScnPlanBody) for b in cache.values())
-    elif mode == "2":
-        assert all(isinstance(h, S._ScnHead) and len(h.tails) == 1 and
-                   all(t.graph is not None for t in h.tails.values()) for h in cache.values())
     else:
         assert all(isinstance(b, S._ScnBody) for b in cache.values())
     with torch.no_grad():
@@ -235,6 +231,32 @@ def _graph_replay_equals_eager(cuda, residual, mode, monkeypatch, inp, part, abo
     for _ in range(2):
         assert torch.equal(run(inp, True), run(inp, False))
     assert len(cache) == 3
+
+
+def test_scn_default_mode_batched_falls_back_to_single_graph(cuda, monkeypatch):
+    """The default mode (O3DML_SCN_GRAPH unset: 3) on a batch of two — the
+    frame and two thirds of its points: the plan takes one batch element, so
+    the forward goes through mode 1's path (one _ScnBody over both elements,
+    nothing captured by the plan) and equals the eager forward bit for bit on
+    the first sighting, the capture and the replay."""
+    from o3dml_amd import sparseconvnet as S
+    m = _model(True, cuda)
+    inp = _inputs(cuda)
+    n = inp.point[0].shape[0]
+    keep = torch.randperm(n, generator=torch.Generator(device="cpu").manual_seed(1))[: n * 2 // 3].to(cuda)
+    batch = types.SimpleNamespace(point=[inp.point[0], inp.point[0][keep].contiguous()],
+                                  feat=[inp.feat[0], inp.feat[0][keep].contiguous()],
+                                  batch_lengths=[n, keep.shape[0]])
+    for frame in ("first sighting", "capture", "replay"):
+        monkeypatch.delenv("O3DML_SCN_GRAPH", raising=False)
+        with torch.no_grad():
+            out = m(batch).clone()
+        monkeypatch.setenv("O3DML_SCN_GRAPH", "0")
+        with torch.no_grad():
+            assert torch.equal(out, m(batch)), frame
+    single = m.__dict__["_o3dml_scn_single"]
+    assert len(single) == 1 and all(isinstance(b, S._ScnBody) and b.graph is not None for b in single.values())
+    assert not m.__dict__.get("_o3dml_scn_plan_bodies")
 
 
 def test_scn_plan_matches_input_layer_and_grids(cuda):
@@ -257,7 +279,7 @@ def test_scn_plan_matches_input_layer_and_grids(cuda):
         assert torch.equal(half, p)
 
 
-@pytest.mark.parametrize("mode", ["1", "2", "3"])
+@pytest.mark.parametrize("mode", ["1", "3"])
 @pytest.mark.parametrize("cols", [6, 70])
 def test_scn_extra_feature_columns(cuda, cols, mode, monkeypatch):
     """Feature rows wider than three columns: the InputLayer averages columns
@@ -279,11 +301,11 @@ def test_scn_extra_feature_columns(cuda, cols, mode, monkeypatch):
     for frame in ("first sighting", "capture", "replay"):
         with torch.no_grad():
             assert torch.equal(m(wide), ref), frame
-    name = {"1": "_o3dml_scn_single", "2": "_o3dml_scn_bodies", "3": "_o3dml_scn_plan_bodies"}[mode]
+    name = {"1": "_o3dml_scn_single", "3": "_o3dml_scn_plan_bodies"}[mode]
     assert all(b.graph is not None for b in m.__dict__[name].values()) and len(m.__dict__[name]) == 1
 
 
-@pytest.mark.parametrize("mode", ["1", "2", "3"])
+@pytest.mark.parametrize("mode", ["1", "3"])
 def test_scn_replaced_weights_invalidate_graph(cuda, mode, monkeypatch):
     """Parameters / buffers replaced by OTHER tensors (not modified in place)
     after a graph was captured and replayed: load_state_dict(assign=True), a
@@ -314,7 +336,7 @@ def test_scn_replaced_weights_invalidate_graph(cuda, mode, monkeypatch):
         assert fresh._version == 0 and bn.running_var._version == 0
         bn.running_var = fresh
 
-    name = {"1": "_o3dml_scn_single", "2": "_o3dml_scn_bodies", "3": "_o3dml_scn_plan_bodies"}[mode]
+    name = {"1": "_o3dml_scn_single", "3": "_o3dml_scn_plan_bodies"}[mode]
     for change in (load_assign, new_parameter, new_buffer):
         before = [run(True) for _ in range(3)][-1]  # first sighting, capture, replay
         assert all(b.graph is not None for b in m.__dict__[name].values()) and len(m.__dict__[name]) == 1

@@ -27,6 +27,22 @@ def test_state_dict_manifest(tag, residual):
     assert [",".join(map(str, v.shape)) for v in sd.values()] == [str(s) for s in G[f"{tag}_shapes"]]
 
 
+def test_graph_mode_rejects_unknown_values(monkeypatch):
+    """O3DML_SCN_GRAPH takes "0", "1", "3" or nothing (= "3"); "2" (a removed
+    mode) and any other value raise and name the three."""
+    from o3dml_amd.sparseconvnet import _graph_mode
+    monkeypatch.delenv("O3DML_SCN_GRAPH", raising=False)
+    assert _graph_mode() == "3"
+    for mode in ("0", "1", "3"):
+        monkeypatch.setenv("O3DML_SCN_GRAPH", mode)
+        assert _graph_mode() == mode
+    for mode in ("2", "on"):
+        monkeypatch.setenv("O3DML_SCN_GRAPH", mode)
+        with pytest.raises(ValueError) as err:
+            _graph_mode()
+        assert all(f'"{ok}"' in str(err.value) for ok in ("0", "1", "3")) and repr(mode) in str(err.value)
+
+
 def test_replaced_tensors_drop_the_eval_caches():
     """A parameter or buffer replaced by another tensor object (not modified
     in place) changes _param_key and drops whatever was captured on the old
