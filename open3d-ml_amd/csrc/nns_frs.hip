@@ -123,11 +123,18 @@ constexpr int kCandCap = 256;
 // Slot table of the run leaders of a chunk (words of the candidate list, past
 // the group tables and segment list of the set-up): 512 slots
 constexpr uint32_t kRunSlot0 = 512, kRunSlots = 512;
+// Run table of the stream cursor: the entry rode whole in the previous entry's
+// last round (bit 31 is free: point indices reach 2 n_pts + 1 < 2^32)
+constexpr uint32_t kEntryRode = 0x80000000u;
 
 // The value of the lane to the left (DPP wave_shr:1); lane 0 keeps its own.
 __device__ __forceinline__ uint32_t left_lane(uint32_t v) {
     return static_cast<uint32_t>(
             __builtin_amdgcn_update_dpp(static_cast<int>(v), static_cast<int>(v), 0x138, 0xF, 0xF, false));
+}
+// The same, lane 0 takes 0.
+__device__ __forceinline__ uint32_t left_lane_or0(uint32_t v) {
+    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x138, 0xF, 0xF, false));
 }
 __device__ __forceinline__ float rdlane_f(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -385,11 +392,15 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
             if constexpr (MODE == 1) qrow[mytag >> 16] = row;
         }
         // 3. The groups in order.  Their bucket lists are built a batch at a
-        //    time, for the next (up to) seven groups in one pass: vst / vlen hold
-        //    the batch's lists one after the other, each followed by a zero entry,
-        //    and bit 9 t + k of km says that visited bin k of the batch's t-th
-        //    group is a live segment.
-        uint32_t vst = 0, vlen = 0;
+        //    time, for the next (up to) seven groups in one pass: the batch's
+        //    lists (start, length) one after the other, each followed by a zero
+        //    entry, and bit 9 t + k of km says that visited bin k of the batch's
+        //    t-th group is a live segment.  Lane i of vrun / vrem keeps entry i
+        //    as the stream cursor meets it: the first point the previous
+        //    entry's last round has not taken and the number of points from
+        //    there on, or kEntryRode | length for an entry that went whole into
+        //    that round (the zero entries among them).
+        uint32_t vrun = 0, vrem = 0;
         float vbox = 0.f;  // lane 8 t + d: word d of the box of the batch's t-th group (min x, y, z, max x, y, z)
         uint64_t km = 0;
         int gi = 0, nbat = 0;  // group within the batch, groups of the batch
@@ -499,7 +510,22 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
                 if (live && tg < nbat) seg[mbcnt64(km) + tg] = make_uint2(st, ln);
                 __syncthreads();
                 const uint2 sg = seg[bl];
-                vst = sg.x, vlen = sg.y;
+                // Run tables of the stream cursor.  A round that ends entry i - 1
+                // with t points also takes the first 64 - t points of entry i, so
+                // h = min(len_i, room_{i-1}) points of entry i are gone when the
+                // cursor enters it, and entry i leaves room_i = (h - len_i) mod 64
+                // lanes to the next one (0 when it went whole into that round,
+                // which starts the next entry afresh; 0 after a zero entry, so h
+                // restarts with every list).  A list has at most nine entries:
+                // eight steps along the lanes settle every list of the batch.
+                uint32_t room = (zero - sg.y) & 63u, h = zero;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    h = min(sg.y, left_lane_or0(room));
+                    room = (h - sg.y) & 63u;
+                }
+                vrun = sg.x + h;
+                vrem = h == sg.y ? kEntryRode | sg.y : sg.y - h;
                 __syncthreads();
                 gi = 0;
             }
@@ -544,30 +570,44 @@ frs_group_kernel(const float4* __restrict__ pts, uint32_t n_pts, const uint32_t*
 #endif
             // stop filling while the next round (and the test padding) might not fit
             const int fill_lim = kCandCap - 64 * kStreamU - (S - 1);
-            // Stream cursor (uniform): bucket bk, boff of its entries consumed.  A
-            // round of 64 lanes takes the rest of bucket bk (lanes < t) and the
-            // head of bucket bk + 1, never more than two buckets; lanes past the
-            // group's buckets (or past bucket bk + 1) read the far sentinel.
-            uint32_t boff = 0;
+            // Stream cursor (uniform): bucket bk, its next point cur, rem points
+            // left.  A round of 64 lanes takes the rest of bucket bk (lanes < t)
+            // and the head of bucket bk + 1, never more than two buckets; lanes
+            // past the group's buckets (or past bucket bk + 1) read the far
+            // sentinel.  What the round takes of bucket bk + 1 is in the run
+            // tables: all of it (then the cursor skips it), or the 64 - t points
+            // its entry already leaves out.
+            uint32_t cur = rdlane(static_cast<int>(vrun), bk), rem = rdlane(static_cast<int>(vrem), bk);
+            // Only ifs without an else, and every value set before them: the fill
+            // loop has lane-dependent branches, so the compiler lays its uniform
+            // branches out the same way, and an if / else or an early return
+            // costs flag registers, moves and placeholder reads in every round.
             auto round_src = [&]() -> uint32_t {
-                if (bk >= nbk) return n_pts;
-                const uint32_t st0 = rdlane(static_cast<int>(vst), bk) + boff;
-                const uint32_t t = rdlane(static_cast<int>(vlen), bk) - boff;
-                if (t > 64) {
-                    boff += 64;
-                    return st0 + lane;
+                uint32_t src = n_pts;
+                if (bk < nbk) {
+                    const uint32_t t = rem;
+                    src = cur + lane;
+                    cur += 64, rem -= 64;  // a whole round of bucket bk
+                    if (t <= 64) {         // its last one: lanes from t on take the head of bucket bk + 1
+                        uint32_t run1 = rdlane(static_cast<int>(vrun), bk + 1);
+                        uint32_t rem1 = rdlane(static_cast<int>(vrem), bk + 1);
+                        const bool rode = (rem1 & kEntryRode) != 0u;
+                        const uint32_t end = rode ? t + (rem1 & 63u) : 64u;  // lanes of the round in use
+                        // run1 is the point after the head, which has end - t points and starts at lane t
+                        // (pinned in an SGPR, or it is subtracted per lane)
+                        uint32_t d1 = run1 - end;
+                        asm volatile("" : "+s"(d1));
+                        src = static_cast<uint32_t>(lane) < t ? src : d1 + lane;
+                        src = static_cast<uint32_t>(lane) < end ? src : n_pts;
+                        bk += 1;
+                        if (rode) {
+                            bk += 1;
+                            run1 = rdlane(static_cast<int>(vrun), bk), rem1 = rdlane(static_cast<int>(vrem), bk);
+                        }
+                        cur = run1, rem = rem1;
+                    }
                 }
-                const uint32_t n1 = rdlane(static_cast<int>(vlen), bk + 1);  // 0 past the list
-                const uint32_t d1 = rdlane(static_cast<int>(vst), bk + 1) - t;
-                const uint32_t src = static_cast<uint32_t>(lane) < t ? st0 + lane : d1 + lane;
-                if (t + n1 <= 64) {
-                    bk += 2;
-                    boff = 0;
-                } else {
-                    bk += 1;
-                    boff = 64 - t;
-                }
-                return static_cast<uint32_t>(lane) < t + n1 ? src : n_pts;
+                return src;
             };
             // all addresses of a step first, then all its loads (in flight together)
             auto load_step = [&](float4* c, auto buf) {
