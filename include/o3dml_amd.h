@@ -275,7 +275,9 @@ int o3dml_dense_act(const float* a1, int k1, const float* a2, int k2, const int6
  * (ml3d/torch/models/point_pillars.py:352-357, sparseconvnet.py:293-298).
  * points f32 [N, ndim] (ndim <= 8); voxel_size / range_min / range_max are
  * HOST arrays of ndim floats.  Canonical semantics: coord_d =
- * floor((p_d - min_d) / vs_d) in double, valid iff 0 <= coord_d < extent_d,
+ * floor((p_d - min_d) * (1 / vs_d)) in double (the reciprocal rounded once,
+ * so equal to the quotient for power-of-two sizes), extent_d =
+ * trunc((max_d - min_d) * (1 / vs_d)), valid iff 0 <= coord_d < extent_d,
  * voxels ordered by (batch, linear id with dim 0 fastest), points of a voxel
  * by index; first max_voxels voxels per batch item, first
  * max_points_per_voxel points per voxel.  _count writes counts_host[0] = V,

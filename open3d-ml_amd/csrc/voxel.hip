@@ -427,7 +427,10 @@ inline VoxParams make_vox_params(int ndim, int nb, const float* vs, const float*
         vp.ext[d] = static_cast<int32_t>((static_cast<double>(mx[d]) - static_cast<double>(mn[d])) * vp.inv[d]);
         if (vp.ext[d] < 0) vp.ext[d] = 0;
         vp.stride[d] = h;
-        h *= vp.ext[d];
+        // saturating: 8 dims of 2^10 cells would wrap int64 to 0 and pass the
+        // key-budget check below as an empty grid
+        constexpr int64_t kCap = int64_t(1) << 56;
+        h = vp.ext[d] == 0 ? 0 : (h <= (kCap - 1) / vp.ext[d] ? h * vp.ext[d] : kCap);
         // power-of-two strides: the same order of (batch, coordinates) keys,
         // each coordinate in whole bits, so only the digits its values vary in
         // need a sort pass (the keys' OR / AND plan the passes)
