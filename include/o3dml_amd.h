@@ -371,6 +371,62 @@ int o3dml_three_interpolate_grad_det(const float* grad_out, const int32_t* idx, 
                                      int64_t C, int64_t n, int64_t m, float* grad_features, void* workspace,
                                      size_t workspace_bytes, void* stream);
 
+/* Ragged farthest-point sampling: replaces furthest_point_sample_v2
+ * (pointnet2_utils.py:89-99, called at point_transformer.py:518), a host loop
+ * over the clouds with one launch and host reads of row_splits each.  xyz f32
+ * [n,3]; row_splits / new_row_splits int64 [B+1] on the DEVICE; max_n the
+ * largest cloud and m_total = new_row_splits[B], host values.  One launch, one
+ * workgroup per cloud: out int32 [m_total] receives cloud b's samples as
+ * global rows (local index + row_splits[b]) at new_row_splits[b].  int32 is
+ * what the reference's expression yields: an int32 tensor plus a 0-dim int64
+ * tensor stays int32 under torch's type promotion (0-dim operands of the same
+ * category do not widen).  Per cloud bit-identical to
+ * o3dml_furthest_point_sampling on that cloud alone, whichever register
+ * variant max_n selects (ties -> smallest index).  A cloud that asks for 0
+ * samples writes nothing; an empty cloud that asks for samples is the
+ * caller's error (the kernel writes nothing for it and reads nothing). */
+size_t o3dml_furthest_point_sampling_ragged_workspace_size(int64_t n, int64_t max_n);
+int o3dml_furthest_point_sampling_ragged(const float* xyz, int64_t n, int64_t B, const int64_t* row_splits,
+                                         const int64_t* new_row_splits, int64_t max_n, int64_t m_total, int32_t* out,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- PointTransformer inference ops (ml3d/torch/models/point_transformer.py,
+ * eval() forward).  Contiguous float32 unless noted; idx int32 [n, nsample]
+ * holds source rows in [0, n_src): the kernels trust it (the Python plan
+ * object checks it once).  xyz_q f32 [n,3] are the queries, xyz_src f32
+ * [n_src,3] the points the rows of idx name.  The positional encoding of a
+ * pair, p_r(i,j) = w2 relu(scale_p * (w1 (xyz_src[idx[i,j]] - xyz_q[i]) + b1)
+ * + shift_p) + b2, is linear_p (:399-404) with its BatchNorm1d(3) folded to
+ * scale_p / shift_p [3] by the caller; w1 [3,3], b1 [3], w2 [c,3], b2 [c]
+ * (torch Linear layouts).  It is recomputed per lane and never stored.
+ * Limits (status code, before any launch): 1 <= nsample <= 64, c a multiple
+ * of share_planes, 1 <= k <= 8 for the interpolation.  Sums run over the
+ * neighbours in index order: bitwise reproducible, no atomics.
+ * relation (:430-453 and linear_w[0:2], replaces the grouped k, point_r and
+ *   their sum): out [n,nsample,c] = relu(scale_w * ((feat_k[idx[i,j]] -
+ *   feat_q[i]) + p_r(i,j)) + shift_w), scale_w / shift_w [c] the folded first
+ *   BatchNorm of linear_w.
+ * aggregate (:461-465): out [n,c], out[i,ch] = sum_j softmax_j(weight[i,:,ch
+ *   mod (c / share_planes)])_j * (feat_v[idx[i,j],ch] + p_r(i,j)[ch]), weight
+ *   [n,nsample,c/share_planes], the softmax over j with the maximum subtracted.
+ * knn_interpolate (:737-776): out [n,c] = sum_t w_t feat[idx[i,t]], w_t = r_t
+ *   / sum_t r_t, r_t = 1 / (dist[i,t] + 1e-8), idx / dist [n,k] as knn_search
+ *   returns them (squared distance for L2).
+ * group (queryandgroup :650-697 with use_xyz, for :521-532): out
+ *   [n,nsample,3+c] = [xyz_src[idx[i,j]] - xyz_q[i] | feat[idx[i,j]]]. */
+int o3dml_pt_relation(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat_k,
+                      const float* feat_q, const float* w1, const float* b1, const float* scale_p,
+                      const float* shift_p, const float* w2, const float* b2, const float* scale_w,
+                      const float* shift_w, int64_t n, int64_t nsample, int64_t c, float* out, void* stream);
+int o3dml_pt_aggregate(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat_v,
+                       const float* weight, const float* w1, const float* b1, const float* scale_p,
+                       const float* shift_p, const float* w2, const float* b2, int64_t n, int64_t nsample, int64_t c,
+                       int64_t share_planes, float* out, void* stream);
+int o3dml_pt_knn_interpolate(const float* feat, const int32_t* idx, const float* dist, int64_t n, int64_t k,
+                             int64_t c, float* out, void* stream);
+int o3dml_pt_group(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat, int64_t n,
+                   int64_t nsample, int64_t c, float* out, void* stream);
+
 /* ---- rotated BEV NMS: replaces open3d.ml.torch.ops.nms
  * (ml3d/torch/utils/objdet_helper.py:27, called by multiclass_nms :346 from
  * point_pillars.py:1005).  boxes f32 [N,5] (x1,y1,x2,y2,yaw), scores f32 [N];

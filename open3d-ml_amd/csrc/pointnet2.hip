@@ -25,12 +25,13 @@ __device__ __forceinline__ void argmax_merge(float& v, int& i, float v2, int i2)
     }
 }
 
+// One cloud of n points at p, m samples to o, each written as index + add.
+// Which ITEMS serves a cloud does not change its result: a lane keeps the
+// first of equal distances among its own points (ascending), the merges keep
+// the smallest index, and no arithmetic touches the distances on the way.
 template <int ITEMS>
-__global__ void __launch_bounds__(kFpsThreads) fps_kernel(const float* __restrict__ xyz, int n, int m,
-                                                          int32_t* __restrict__ out) {
-    const int b = blockIdx.x;
-    const float* p = xyz + static_cast<int64_t>(b) * n * 3;
-    int32_t* o = out + static_cast<int64_t>(b) * m;
+__device__ __forceinline__ void fps_cloud(const float* __restrict__ p, int n, int m, int32_t* __restrict__ o,
+                                          int add) {
     const int t = threadIdx.x;
     float px[ITEMS], py[ITEMS], pz[ITEMS], md[ITEMS];
 #pragma unroll
@@ -47,7 +48,7 @@ __global__ void __launch_bounds__(kFpsThreads) fps_kernel(const float* __restric
     __shared__ int s_old;
     if (m <= 0) return;
     int old = 0;
-    if (t == 0) o[0] = 0;
+    if (t == 0) o[0] = add;
     for (int j = 1; j < m; ++j) {
         const float x1 = p[3 * old], y1 = p[3 * old + 1], z1 = p[3 * old + 2];
         float best = -1.f;
@@ -85,7 +86,7 @@ __global__ void __launch_bounds__(kFpsThreads) fps_kernel(const float* __restric
             }
             if (t == 0) {
                 s_old = i;
-                o[j] = i;
+                o[j] = i + add;
             }
         }
         __syncthreads();
@@ -93,13 +94,29 @@ __global__ void __launch_bounds__(kFpsThreads) fps_kernel(const float* __restric
     }
 }
 
-// Fallback for very large clouds: min-distances in global memory.
-__global__ void __launch_bounds__(kFpsThreads) fps_global_kernel(const float* __restrict__ xyz, int n, int m,
-                                                                 float* __restrict__ temp, int32_t* __restrict__ out) {
+template <int ITEMS>
+__global__ void __launch_bounds__(kFpsThreads) fps_kernel(const float* __restrict__ xyz, int n, int m,
+                                                          int32_t* __restrict__ out) {
     const int b = blockIdx.x;
-    const float* p = xyz + static_cast<int64_t>(b) * n * 3;
-    float* md = temp + static_cast<int64_t>(b) * n;
-    int32_t* o = out + static_cast<int64_t>(b) * m;
+    fps_cloud<ITEMS>(xyz + static_cast<int64_t>(b) * n * 3, n, m, out + static_cast<int64_t>(b) * m, 0);
+}
+
+// Ragged batch: cloud b is rows row_splits[b] .. row_splits[b+1] of xyz and
+// gets new_row_splits[b+1] - new_row_splits[b] samples, written as global rows.
+template <int ITEMS>
+__global__ void __launch_bounds__(kFpsThreads)
+fps_ragged_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ row_splits,
+                  const int64_t* __restrict__ new_row_splits, int32_t* __restrict__ out) {
+    const int b = blockIdx.x;
+    const int64_t r0 = row_splits[b], o0 = new_row_splits[b];
+    const int n = static_cast<int>(row_splits[b + 1] - r0), m = static_cast<int>(new_row_splits[b + 1] - o0);
+    if (n <= 0 || n > ITEMS * kFpsThreads) return;
+    fps_cloud<ITEMS>(xyz + r0 * 3, n, m, out + o0, static_cast<int>(r0));
+}
+
+// Fallback for very large clouds: min-distances in global memory.
+__device__ __forceinline__ void fps_cloud_global(const float* __restrict__ p, int n, int m, float* __restrict__ md,
+                                                 int32_t* __restrict__ o, int add) {
     const int t = threadIdx.x;
     __shared__ float sv[kFpsThreads / 64];
     __shared__ int si[kFpsThreads / 64];
@@ -107,7 +124,7 @@ __global__ void __launch_bounds__(kFpsThreads) fps_global_kernel(const float* __
     for (int k = t; k < n; k += kFpsThreads) md[k] = 1e10f;
     if (m <= 0) return;
     int old = 0;
-    if (t == 0) o[0] = 0;
+    if (t == 0) o[0] = add;
     __syncthreads();
     for (int j = 1; j < m; ++j) {
         const float x1 = p[3 * old], y1 = p[3 * old + 1], z1 = p[3 * old + 2];
@@ -144,12 +161,30 @@ __global__ void __launch_bounds__(kFpsThreads) fps_global_kernel(const float* __
             }
             if (t == 0) {
                 s_old = i;
-                o[j] = i;
+                o[j] = i + add;
             }
         }
         __syncthreads();
         old = s_old;
     }
+}
+
+__global__ void __launch_bounds__(kFpsThreads) fps_global_kernel(const float* __restrict__ xyz, int n, int m,
+                                                                 float* __restrict__ temp, int32_t* __restrict__ out) {
+    const int b = blockIdx.x;
+    fps_cloud_global(xyz + static_cast<int64_t>(b) * n * 3, n, m, temp + static_cast<int64_t>(b) * n,
+                     out + static_cast<int64_t>(b) * m, 0);
+}
+
+__global__ void __launch_bounds__(kFpsThreads)
+fps_ragged_global_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ row_splits,
+                         const int64_t* __restrict__ new_row_splits, float* __restrict__ temp,
+                         int32_t* __restrict__ out) {
+    const int b = blockIdx.x;
+    const int64_t r0 = row_splits[b], o0 = new_row_splits[b];
+    const int n = static_cast<int>(row_splits[b + 1] - r0), m = static_cast<int>(new_row_splits[b + 1] - o0);
+    if (n <= 0) return;
+    fps_cloud_global(xyz + r0 * 3, n, m, temp + r0, out + o0, static_cast<int>(r0));
 }
 
 constexpr int kTile = 256;
@@ -346,6 +381,40 @@ O3DML_API int o3dml_furthest_point_sampling(const float* xyz, int64_t B, int64_t
         Workspace ws(workspace, workspace_bytes);
         float* temp = ws.take<float>(B * n);
         fps_global_kernel<<<g, kFpsThreads, 0, st>>>(xyz, ni, mi, temp, out);
+    }
+    O3DML_LAUNCH_CHECK();
+    O3DML_GUARD_END
+}
+
+O3DML_API size_t o3dml_furthest_point_sampling_ragged_workspace_size(int64_t n, int64_t max_n) {
+    return max_n > 32 * kFpsThreads ? ws_bytes<float>(n) : 0;
+}
+
+// xyz f32 [n,3], device row_splits / new_row_splits int64 [B+1] -> out int32
+// [new_row_splits[B]] (global rows); max_n: the largest cloud, from the host
+O3DML_API int o3dml_furthest_point_sampling_ragged(const float* xyz, int64_t n, int64_t B, const int64_t* row_splits,
+                                                   const int64_t* new_row_splits, int64_t max_n, int64_t m_total,
+                                                   int32_t* out, void* workspace, size_t workspace_bytes,
+                                                   void* stream) {
+    O3DML_GUARD_BEGIN
+    O3DML_REQUIRE(max_n > 0 || m_total == 0, "furthest_point_sampling_ragged: empty cloud");
+    O3DML_REQUIRE(n < (int64_t(1) << 31) && max_n <= n && m_total < (int64_t(1) << 31),
+                  "furthest_point_sampling_ragged: too large");
+    if (B == 0 || m_total == 0) return 0;
+    hipStream_t st = as_stream(stream);
+    TimedRegion tr("fps_ragged", st);
+    const int items = static_cast<int>(ceil_div(max_n, kFpsThreads));
+    dim3 g(static_cast<unsigned>(B));
+    if (items <= 1) fps_ragged_kernel<1><<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, out);
+    else if (items <= 2) fps_ragged_kernel<2><<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, out);
+    else if (items <= 4) fps_ragged_kernel<4><<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, out);
+    else if (items <= 8) fps_ragged_kernel<8><<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, out);
+    else if (items <= 16) fps_ragged_kernel<16><<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, out);
+    else if (items <= 32) fps_ragged_kernel<32><<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, out);
+    else {
+        Workspace ws(workspace, workspace_bytes);
+        float* temp = ws.take<float>(n);
+        fps_ragged_global_kernel<<<g, kFpsThreads, 0, st>>>(xyz, row_splits, new_row_splits, temp, out);
     }
     O3DML_LAUNCH_CHECK();
     O3DML_GUARD_END
