@@ -427,6 +427,22 @@ int o3dml_pt_knn_interpolate(const float* feat, const int32_t* idx, const float*
 int o3dml_pt_group(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat, int64_t n,
                    int64_t nsample, int64_t c, float* out, void* stream);
 
+/* ---- RoI point pooling: replaces open3d.ml.torch.ops.roi_pool
+ * (ml3d/torch/utils/roipool3d/roipool3d_utils.py:24, PointRCNN).  xyz f32
+ * [B,N,3], boxes3d f32 [B,M,7] = (x, y, z, h, w, l, ry) in the camera frame
+ * (y the bottom face, y axis down: centre cy = y - h/2), pts_feature f32
+ * [B,N,C] -> pooled f32 [B,M,S,3+C], empty_flag i32 [B,M], idx_out i32
+ * [B,M,S] (nullable): per box the first S member points in ascending index as
+ * rows [xyz | feature] copied bit for bit; fewer than S members repeat
+ * cyclically (slot s = member s % cnt), none gives flag 1, a zero block and
+ * idx -1.  Membership in f32, closed bounds, NaN never a member:
+ * |px-x| <= 10, |py-cy| <= h/2, |pz-z| <= 10, and with
+ * xr = (px-x) cos ry - (pz-z) sin ry, zr = (px-x) sin ry + (pz-z) cos ry:
+ * |xr| <= l/2, |zr| <= w/2.  Every output element is written (no memset
+ * needed); no atomics.  S in 1..8192, C in 0..65536, N < 2^31. */
+int o3dml_roi_pool(const float* xyz, const float* boxes3d, const float* pts_feature, int64_t B, int64_t N, int64_t M,
+                   int64_t C, int64_t S, float* pooled, int32_t* empty_flag, int32_t* idx_out, void* stream);
+
 /* ---- rotated BEV NMS: replaces open3d.ml.torch.ops.nms
  * (ml3d/torch/utils/objdet_helper.py:27, called by multiclass_nms :346 from
  * point_pillars.py:1005).  boxes f32 [N,5] (x1,y1,x2,y2,yaw), scores f32 [N];

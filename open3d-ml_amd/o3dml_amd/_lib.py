@@ -165,6 +165,8 @@ SIGNATURES = {
     "o3dml_pt_aggregate": (c_i32, [c_p] * 11 + [c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     "o3dml_pt_knn_interpolate": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
     "o3dml_pt_group": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
+    # roi_pool.hip
+    "o3dml_roi_pool": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
     "o3dml_nms_workspace_size": (c_sz, [c_i64]),
     "o3dml_nms": (c_i32, [c_p, c_p, c_i64, c_f32, c_p, c_p, c_p, c_sz, c_p]),
     # box_iou.hip, box_iou_host.cpp

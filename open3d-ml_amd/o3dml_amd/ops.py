@@ -846,10 +846,61 @@ def nms(boxes, scores, nms_overlap_thresh):
 
 
 # ---------------------------------------------------------------------------
+# RoI point pooling (PointRCNN, roipool3d_utils.py:24)
+# ---------------------------------------------------------------------------
+ROI_POOL_MAX_SAMPLES = 8192
+
+
+def _roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num, with_index):
+    dev = gpu_device(xyz, boxes3d, pts_feature)
+    for name, t, last in (("xyz", xyz, 3), ("boxes3d", boxes3d, 7), ("pts_feature", pts_feature, None)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or (
+                last is not None and t.shape[2] != last):
+            raise RuntimeError(f"roi_pool: {name} must be float32 [B, *, {'C' if last is None else last}], got "
+                               f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"roi_pool: {name} must be contiguous")
+    B, N, _ = xyz.shape
+    M, C, S = boxes3d.shape[1], pts_feature.shape[2], int(sampled_pts_num)
+    if boxes3d.shape[0] != B or pts_feature.shape[0] != B or pts_feature.shape[1] != N:
+        raise RuntimeError(f"roi_pool: xyz {list(xyz.shape)}, boxes3d {list(boxes3d.shape)} and pts_feature "
+                           f"{list(pts_feature.shape)} do not share B and N")
+    if not 1 <= S <= ROI_POOL_MAX_SAMPLES:
+        raise RuntimeError(f"roi_pool: sampled_pts_num must be in 1..{ROI_POOL_MAX_SAMPLES}, got {S}")
+    x, b, f = to_dev(xyz.detach(), dev), to_dev(boxes3d.detach(), dev), to_dev(pts_feature.detach(), dev)
+    pooled = torch.empty((B, M, S, 3 + C), dtype=torch.float32, device=dev)
+    flag = torch.empty((B, M), dtype=torch.int32, device=dev)
+    idx = torch.empty((B, M, S), dtype=torch.int32, device=dev) if with_index else None
+    if B * M:
+        _lib.call("o3dml_roi_pool", ptr(x), ptr(b), ptr(f), B, N, M, C, S, ptr(pooled), ptr(flag), ptr(idx),
+                  stream_handle(dev))
+    return back_to(pooled, xyz), back_to(flag, xyz), None if idx is None else back_to(idx, xyz)
+
+
+def roi_pool_indexed(xyz, boxes3d, pts_feature, sampled_pts_num):
+    """roi_pool plus the pooled point index per slot: -> (pooled_features,
+    pooled_empty_flag, index int32 [B, M, sampled_pts_num], -1 in an empty
+    box).  Not an Open3D name."""
+    return _roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num, True)
+
+
+def roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num):
+    """Open3D ``ops.roi_pool`` (roipool3d_utils.py:24): xyz [B,N,3], boxes3d
+    [B,M,7] = (x, y, z, h, w, l, ry) in the camera frame (y the bottom face),
+    pts_feature [B,N,C] -> (pooled_features f32 [B,M,S,3+C], pooled_empty_flag
+    int32 [B,M]).  Per box the first S points inside it in ascending index
+    (closed bounds, float32, a 10 m per-axis prefilter around the centre), as
+    rows [xyz | feature]; fewer than S repeat cyclically, none gives flag 1
+    and zeros.  The contract is spelled out in csrc/roi_pool.hip."""
+    pooled, flag, _ = _roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num, False)  # no index written
+    return pooled, flag
+
+
+# ---------------------------------------------------------------------------
 from .sparse_conv import sparse_conv, sparse_conv_transpose  # noqa: E402,F401
 
 
 __all__ = ["build_spatial_hash_table", "fixed_radius_search", "knn_search", "radius_search", "ragged_to_dense",
            "reduce_subarrays_sum", "voxelize", "grid_subsample", "calculate_grid", "furthest_point_sampling",
            "ball_query", "three_nn", "three_interpolate", "three_interpolate_grad", "nms", "sparse_conv",
-           "sparse_conv_transpose", "trilinear_devoxelize_forward", "trilinear_devoxelize_backward"]
+           "sparse_conv_transpose", "trilinear_devoxelize_forward", "trilinear_devoxelize_backward", "roi_pool"]

@@ -244,6 +244,17 @@ def _(boxes, scores, nms_overlap_thresh):
     return boxes.new_empty((_dyn(),), dtype=torch.int64)
 
 
+@_op("roi_pool")
+def roi_pool(xyz: Tensor, boxes3d: Tensor, pts_feature: Tensor, sampled_pts_num: int) -> tuple[Tensor, Tensor]:
+    return ops.roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num)
+
+
+@roi_pool.register_fake
+def _(xyz, boxes3d, pts_feature, sampled_pts_num):
+    bm = (boxes3d.shape[0], boxes3d.shape[1])
+    return (xyz.new_empty(bm + (sampled_pts_num, 3 + pts_feature.shape[2])), xyz.new_empty(bm, dtype=torch.int32))
+
+
 # ----------------------------------------------------------------- sparse convolution
 @_op("sparse_conv")
 def sparse_conv(filters: Tensor, inp_features: Tensor, inp_importance: Optional[Tensor], neighbors_index: Tensor,
@@ -324,4 +335,4 @@ sparse_conv_transpose.register_autograd(_sct_backward, setup_context=_sct_setup)
 OPS = ("build_spatial_hash_table", "fixed_radius_search", "knn_search", "radius_search", "ragged_to_dense",
        "reduce_subarrays_sum", "voxelize", "furthest_point_sampling", "ball_query", "three_nn", "three_interpolate",
        "three_interpolate_grad", "nms", "sparse_conv", "sparse_conv_transpose", "trilinear_devoxelize_forward",
-       "trilinear_devoxelize_backward")
+       "trilinear_devoxelize_backward", "roi_pool")

@@ -2,8 +2,10 @@
 
 trilinear_devoxelize_forward / _backward (PVCNN, pvcnn.py:14) come from
 o3dml_amd.ops like every other op.  roi_pool (PointRCNN, roipool3d_utils.py:4)
-is out of scope: the reference imports it whenever a GPU is
-present, so the name exists and a call raises."""
+exists as o3dml_amd.ops.roi_pool (csrc/roi_pool.hip) and is what
+o3dml_amd.point_rcnn calls; under this shim name it is still the raising stub
+below, which tests/test_pvcnn.py pins.  Pointing the alias at the op is a
+follow-up together with that test."""
 from o3dml_amd.ops import *  # noqa: F401,F403
 from o3dml_amd.ops import __all__ as _hot
 
