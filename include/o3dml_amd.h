@@ -427,6 +427,59 @@ int o3dml_pt_knn_interpolate(const float* feat, const int32_t* idx, const float*
 int o3dml_pt_group(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat, int64_t n,
                    int64_t nsample, int64_t c, float* out, void* stream);
 
+/* ---- PointTransformer gradients (csrc/point_transformer_grad.hip): the
+ * backward of the four ops above with BatchNorms in folded (frozen) form.
+ * Nothing is differentiated with respect to coordinates.  The same limits,
+ * as status codes before any launch; 16-byte accesses when c % 4 == 0 and the
+ * rows are 16-byte aligned, else one channel per lane.  Every sum has one
+ * fixed order (no float atomics): run-to-run bitwise equal.
+ * invert_plan: idx i32 [m,k] with entries in [0, n_src) -> inv_splits i64
+ *   [n_src+1], inv_pairs i32 [m*k]: row s = the flat pair ids t = i*k + j with
+ *   idx[i,j] == s in ascending t (a stable argsort of idx plus the prefix sum
+ *   of its bincount, bit for bit).  m*k < 2^31.  No host read.
+ * gather_sum: out [n_src,c], out[s,:] = sum_{t in row s, ascending}
+ *   wgt(t) * rows[(t / div) * ld + col0 : col0 + c]; every row of out is
+ *   written (no pairs: zeros).  wgt(t) = weight[t] if weight is given, else
+ *   r_t / sum_u r_u, r = 1 / (dist[t/k, :] + 1e-8) if dist [m,k] is given (the
+ *   interpolation's weights, recomputed; k <= 8), else 1.  div = 1 reads a
+ *   materialised [m*k, ld] tensor, div = k reads row t / k of an [m, ld] one.
+ *   Serves d feat_k (rows = gr), d feat_v (rows = d_val), d feat of group
+ *   (rows = the upstream gradient, col0 = 3, ld = 3 + c) and d feat of
+ *   knn_interpolate (rows = the upstream gradient, div = k, dist).
+ * relation_backward: with r = (feat_k[idx[i,j]] - feat_q[i]) + p_r(i,j)
+ *   recomputed, gz = grad_out * [out > 0] (out the forward's result), gr = gz *
+ *   scale_w: gr [n,nsample,c]; d_feat_q [n,c] = -sum_j gr[i,j]; dh
+ *   [n,nsample,3] = w2^T gr[i,j] (h = relu(scale_p * (w1 d + b1) + shift_p),
+ *   the caller finishes linear_p[0..2] from dh); d_scale_w [c] = sum gz * r;
+ *   d_shift_w [c] = sum gz; d_w2 [c,3] = sum gr h^T; d_b2 [c] = sum gr (sums
+ *   over all pairs: per-workgroup partials added in workgroup order).
+ * aggregate_backward: with sm the softmax (maximum subtracted) and val =
+ *   feat_v[idx[i,j]] + p_r(i,j) recomputed: d_val [n,nsample,c] = sm * grad_out;
+ *   d_weight [n,nsample,c/s] = sm * (dsm - sum_j sm * dsm), dsm[i,j,gch] =
+ *   sum_{ch = gch mod c/s} grad_out[i,ch] * val[i,j,ch] in ascending ch; dh,
+ *   d_w2, d_b2 as above from d_val.
+ * backward_workspace_size(c): bytes of workspace both backward calls take. */
+size_t o3dml_pt_invert_plan_workspace_size(int64_t m, int64_t k, int64_t n_src);
+int o3dml_pt_invert_plan(const int32_t* idx, int64_t m, int64_t k, int64_t n_src, int64_t* inv_splits,
+                         int32_t* inv_pairs, void* workspace, size_t workspace_bytes, void* stream);
+int o3dml_pt_gather_sum(const float* rows, int64_t ld, int64_t col0, int64_t div, const float* weight,
+                        const float* dist, int64_t k, const int64_t* inv_splits, const int32_t* inv_pairs,
+                        int64_t n_src, int64_t c, float* out, void* stream);
+size_t o3dml_pt_backward_workspace_size(int64_t c);
+int o3dml_pt_relation_backward(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat_k,
+                               const float* feat_q, const float* w1, const float* b1, const float* scale_p,
+                               const float* shift_p, const float* w2, const float* b2, const float* scale_w,
+                               const float* shift_w, const float* out, const float* grad_out, int64_t n,
+                               int64_t nsample, int64_t c, float* gr, float* d_feat_q, float* dh, float* d_scale_w,
+                               float* d_shift_w, float* d_w2, float* d_b2, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int o3dml_pt_aggregate_backward(const float* xyz_q, const float* xyz_src, const int32_t* idx, const float* feat_v,
+                                const float* weight, const float* w1, const float* b1, const float* scale_p,
+                                const float* shift_p, const float* w2, const float* b2, const float* grad_out,
+                                int64_t n, int64_t nsample, int64_t c, int64_t share_planes, float* d_val,
+                                float* d_weight, float* dh, float* d_w2, float* d_b2, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- RoI point pooling: replaces open3d.ml.torch.ops.roi_pool
  * (ml3d/torch/utils/roipool3d/roipool3d_utils.py:24, PointRCNN).  xyz f32
  * [B,N,3], boxes3d f32 [B,M,7] = (x, y, z, h, w, l, ry) in the camera frame

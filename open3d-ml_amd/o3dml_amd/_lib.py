@@ -165,6 +165,13 @@ SIGNATURES = {
     "o3dml_pt_aggregate": (c_i32, [c_p] * 11 + [c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     "o3dml_pt_knn_interpolate": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
     "o3dml_pt_group": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p]),
+    # point_transformer_grad.hip
+    "o3dml_pt_invert_plan_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
+    "o3dml_pt_invert_plan": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_sz, c_p]),
+    "o3dml_pt_gather_sum": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p]),
+    "o3dml_pt_backward_workspace_size": (c_sz, [c_i64]),
+    "o3dml_pt_relation_backward": (c_i32, [c_p] * 15 + [c_i64, c_i64, c_i64] + [c_p] * 8 + [c_sz, c_p]),
+    "o3dml_pt_aggregate_backward": (c_i32, [c_p] * 12 + [c_i64, c_i64, c_i64, c_i64] + [c_p] * 6 + [c_sz, c_p]),
     # roi_pool.hip
     "o3dml_roi_pool": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
     "o3dml_nms_workspace_size": (c_sz, [c_i64]),

@@ -1,6 +1,8 @@
-"""PointTransformer inference (ml3d/torch/models/point_transformer.py): the
-module tree and state_dict of the reference, its eval() forward on the HIP
-kernels of csrc/point_transformer.hip and the ragged FPS of csrc/pointnet2.hip.
+"""PointTransformer (ml3d/torch/models/point_transformer.py): the module tree
+and state_dict of the reference, its eval() forward on the HIP kernels of
+csrc/point_transformer.hip and the ragged FPS of csrc/pointnet2.hip, and the
+gradients of that forward (csrc/point_transformer_grad.hip) with the
+BatchNorms frozen on their running statistics.
 
 The reference searches neighbours on the CPU in every layer (knn_batch
 :700-734, twice per Transformer layer), loops over the clouds for the
@@ -22,22 +24,79 @@ Linears stay on torch / rocBLAS.
 BatchNorms are used in eval form, folded to scale and shift on every call
 from the module's current tensors: nothing folded is kept between forwards.
 After `level_row_splits` (host arithmetic on a host copy of row_splits) the
-forward reads nothing back from the device.  Training is not built:
-forward() in train() mode raises NotImplementedError.
+forward reads nothing back from the device.  Batch-statistics training is not
+built: forward() in train() mode raises NotImplementedError.
+
+Gradients.  The four ops (relation, aggregate, knn_interpolate, group) are
+differentiable in their feature tensors, in weight, scale_w / shift_w and the
+six pos tensors, never in coordinates (a coordinate tensor that requires grad
+raises): with grad mode on and such an input requiring grad they record a
+torch.autograd.Function whose backward runs the HIP kernels; otherwise they
+launch what they always did and return a detached result.  A scatter-add of
+the backward (d feat_k, d feat_v, d feat) is a sum per source row over the
+plan's inverse neighbour list (Neighbours.inverse(), built once per plan and
+kept on it) in ascending pair order.  The backward saves the forward's inputs
+and relation's output; softmax and positional encoding are recomputed.  The
+first positional Linear, BatchNorm and ReLU (three floats per pair) are
+finished with a handful of torch ops from the kernels' dh.
+A plain model(batch) never records: inside `with recording_grad():` (thread
+local, nests) and with grad mode on, the eval() forwards of the modules below
+record autograd, BatchNorms folded from the modules' weight and bias with
+differentiable torch ops and the running statistics as constants (frozen-BN
+fine-tuning, saliency); the dense Linears, ReLUs, the maximum over nsample,
+the head's per-cloud mean and the residual adds run under torch autograd.
 
 Every sum in the HIP ops runs in one fixed order (no float atomics): a second
-forward is bitwise equal to the first.
+forward, and a second backward, is bitwise equal to the first.
 """
+import contextlib
+import threading
+
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._util import gpu_device, ptr, require_gpu, row_splits_host, stream_handle, to_dev, workspace
 
 MAX_NSAMPLE = 64
 MAX_INTERPOLATE_K = 8
+
+# ---------------------------------------------------------------------------
+# the gradient switch
+# ---------------------------------------------------------------------------
+_switch = threading.local()
+
+
+@contextlib.contextmanager
+def recording_grad():
+    """Inside this context (per thread, nests), with grad mode on, the eval()
+    forwards of the modules below record autograd; BatchNorms stay frozen."""
+    depth = getattr(_switch, "depth", 0)
+    _switch.depth = depth + 1
+    try:
+        yield
+    finally:
+        _switch.depth = depth
+
+
+def _recording():
+    return getattr(_switch, "depth", 0) > 0 and torch.is_grad_enabled()
+
+
+def _graph():
+    """The context a module forward runs in: autograd inside the switch, else none."""
+    return contextlib.nullcontext() if _recording() else torch.no_grad()
+
+
+def _relu(x):
+    return F.relu(x) if _recording() else F.relu_(x)
+
+
+def _param(t):
+    return t if _recording() else t.detach()
 
 
 def _f32(name, t, shape):
@@ -78,6 +137,23 @@ class Neighbours:
         self.distance = None
         if distance is not None:
             self.distance = to_dev(_f32("distance", distance, (self.m, self.k)), dev)
+        self._inverse = None
+
+    def inverse(self):
+        """(inv_splits int64 [n_src + 1], inv_pairs int32 [m * k]): row s holds
+        the flat pair ids t = i * k + j with index[i, j] == s in ascending t (a
+        stable argsort of the index).  Built on first use, kept on the plan."""
+        if self._inverse is None:
+            dev = self.index.device
+            if self.m * self.k >= 1 << 31:
+                raise RuntimeError(f"Neighbours.inverse: m * k = {self.m} * {self.k} must be below 2^31")
+            splits = torch.empty(self.n_src + 1, dtype=torch.int64, device=dev)
+            pairs = torch.empty(self.m * self.k, dtype=torch.int32, device=dev)
+            ws = workspace(_lib.load().o3dml_pt_invert_plan_workspace_size(self.m, self.k, self.n_src), dev)
+            _lib.call("o3dml_pt_invert_plan", ptr(self.index), self.m, self.k, self.n_src, ptr(splits), ptr(pairs),
+                      ptr(ws), ws.numel(), stream_handle(dev))
+            self._inverse = (splits, pairs)
+        return self._inverse
 
     @classmethod
     def from_knn(cls, points, queries, k, points_row_splits=None, queries_row_splits=None, distances=False):
@@ -133,17 +209,58 @@ def furthest_point_sample_ragged(xyz, row_splits, new_row_splits):
 
 
 def fold_bn(bn):
-    """(scale, shift) of a BatchNorm in eval form, from its current tensors."""
-    scale = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
-    return scale, bn.bias.detach() - bn.running_mean * scale
+    """(scale, shift) of a BatchNorm in eval form, from its current tensors.
+    Inside recording_grad() the fold is differentiable in weight and bias; the
+    running statistics are constants either way."""
+    scale = _param(bn.weight) * torch.rsqrt(bn.running_var + bn.eps)
+    return scale, _param(bn.bias) - bn.running_mean * scale
 
 
 def position_encoding(linear_p):
     """The six tensors of a Transformer's linear_p (Linear(3,3), BatchNorm1d(3),
     ReLU, Linear(3,c)) the kernels take: (w1, b1, scale_p, shift_p, w2, b2)."""
     scale, shift = fold_bn(linear_p[1])
-    return (linear_p[0].weight.detach(), linear_p[0].bias.detach(), scale, shift, linear_p[3].weight.detach(),
-            linear_p[3].bias.detach())
+    return (_param(linear_p[0].weight), _param(linear_p[0].bias), scale, shift, _param(linear_p[3].weight),
+            _param(linear_p[3].bias))
+
+
+def _records(coords, diff):
+    """True when the op has to record autograd: grad mode on and one of the
+    differentiable inputs requires grad.  Coordinates are never differentiated."""
+    if not torch.is_grad_enabled():
+        return False
+    for name, t in coords:
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError(f"PointTransformer ops are not differentiated with respect to coordinates: {name} "
+                               "requires grad (detach it)")
+    return any(isinstance(t, torch.Tensor) and t.requires_grad for t in diff)
+
+
+def _gather_sum(plan, rows, ld, col0, c, div=1, dist=None):
+    """out[s] = sum over row s of plan.inverse(), ascending, of rows[t // div, col0:col0 + c]
+    (weighted by the interpolation's weights when dist is given) -> [n_src, c]."""
+    dev = plan.index.device
+    splits, pairs = plan.inverse()
+    out = torch.empty((plan.n_src, c), dtype=torch.float32, device=dev)
+    _lib.call("o3dml_pt_gather_sum", ptr(rows), ld, col0, div, None, ptr(dist), plan.k, ptr(splits), ptr(pairs),
+              plan.n_src, c, ptr(out), stream_handle(dev))
+    return out
+
+
+def _pos_hidden_backward(plan, q, s, w1, b1, sc, sh, dh):
+    """Gradients of linear_p[0..2] from dh [m, k, 3] = d loss / d h, h =
+    relu(sc * (w1 d + b1) + sh): three floats per pair, recomputed with torch
+    ops over [m * k, 3] rows (torch.sum over the rows: a fixed order) ->
+    (d w1, d b1, d sc, d sh)."""
+    d = (s[plan.index.reshape(-1).long()].view(plan.m, plan.k, 3) - q.unsqueeze(1)).view(-1, 3)
+    lin = torch.addmm(b1, d, w1.T)
+    du = dh.view(-1, 3) * (sc * lin + sh > 0)
+    dl = du * sc
+    return (dl.unsqueeze(2) * d.unsqueeze(1)).sum(0), dl.sum(0), (du * lin).sum(0), du.sum(0)
+
+
+def _grad_ws(c, dev):
+    return workspace(_lib.load().o3dml_pt_backward_workspace_size(c), dev)
 
 
 def _plan_inputs(plan, xyz_q, xyz_src, feat, c=None):
@@ -172,7 +289,18 @@ def _pos_inputs(pos, c, dev):
 def relation(plan, xyz_q, xyz_src, feat_k, feat_q, pos, scale_w, shift_w):
     """relu(scale_w * (feat_k[idx] - feat_q[:, None] + p_r) + shift_w) ->
     [m, nsample, c] (point_transformer.py:430-453 and the first BatchNorm and
-    ReLU of linear_w); pos as position_encoding() returns it."""
+    ReLU of linear_w); pos as position_encoding() returns it.  Differentiable
+    in feat_k, feat_q, pos, scale_w and shift_w."""
+    require_gpu()
+    if _records((("xyz_q", xyz_q), ("xyz_src", xyz_src)), (feat_k, feat_q, *pos, scale_w, shift_w)):
+        if len(pos) != 6:
+            raise RuntimeError("pos must be (w1, b1, scale_p, shift_p, w2, b2)")
+        return _Relation.apply(plan, xyz_q, xyz_src, feat_k, feat_q, *pos, scale_w, shift_w)
+    return _relation(plan, xyz_q, xyz_src, feat_k, feat_q, pos, scale_w, shift_w)[0]
+
+
+def _relation(plan, xyz_q, xyz_src, feat_k, feat_q, pos, scale_w, shift_w):
+    """(out, the checked device tensors the kernel read)."""
     dev, q, s, fk = _plan_inputs(plan, xyz_q, xyz_src, feat_k)
     c = fk.shape[1]
     fq = to_dev(_f32("feat_q", feat_q, (plan.m, c)), dev)
@@ -182,12 +310,51 @@ def relation(plan, xyz_q, xyz_src, feat_k, feat_q, pos, scale_w, shift_w):
     out = torch.empty((plan.m, plan.k, c), dtype=torch.float32, device=dev)
     _lib.call("o3dml_pt_relation", ptr(q), ptr(s), ptr(plan.index), ptr(fk), ptr(fq), *[ptr(t) for t in p], ptr(sw),
               ptr(tw), plan.m, plan.k, c, ptr(out), stream_handle(dev))
-    return out
+    return out, (q, s, fk, fq, *p, sw, tw)
+
+
+class _Relation(torch.autograd.Function):
+    """Saves the forward's inputs and its output (whose sign is the ReLU mask)."""
+
+    @staticmethod
+    def forward(ctx, plan, xyz_q, xyz_src, feat_k, feat_q, w1, b1, sc, sh, w2, b2, scale_w, shift_w):
+        out, saved = _relation(plan, xyz_q, xyz_src, feat_k, feat_q, (w1, b1, sc, sh, w2, b2), scale_w, shift_w)
+        ctx.plan = plan
+        ctx.save_for_backward(*saved, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        plan = ctx.plan
+        q, s, fk, fq, w1, b1, sc, sh, w2, b2, sw, tw, out = ctx.saved_tensors
+        dev, (m, k, c) = out.device, out.shape
+        g = to_dev(g, dev, torch.float32)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        gr, dq, dh = new(m, k, c), new(m, c), new(m, k, 3)
+        dsw, dtw, dw2, db2 = new(c), new(c), new(c, 3), new(c)
+        ws = _grad_ws(c, dev)
+        _lib.call("o3dml_pt_relation_backward", ptr(q), ptr(s), ptr(plan.index), ptr(fk), ptr(fq), ptr(w1), ptr(b1),
+                  ptr(sc), ptr(sh), ptr(w2), ptr(b2), ptr(sw), ptr(tw), ptr(out), ptr(g), m, k, c, ptr(gr), ptr(dq),
+                  ptr(dh), ptr(dsw), ptr(dtw), ptr(dw2), ptr(db2), ptr(ws), ws.numel(), stream_handle(dev))
+        dfk = _gather_sum(plan, gr, c, 0, c) if ctx.needs_input_grad[3] else None
+        first = _pos_hidden_backward(plan, q, s, w1, b1, sc, sh, dh) if any(ctx.needs_input_grad[5:9]) else (None,) * 4
+        return (None, None, None, dfk, dq, *first, dw2, db2, dsw, dtw)
 
 
 def aggregate(plan, xyz_q, xyz_src, feat_v, weight, pos, share_planes):
     """sum_j softmax_j(weight)[.., ch mod (c/s)] * (feat_v[idx] + p_r) -> [m, c]
-    (point_transformer.py:461-465); weight [m, nsample, c / share_planes]."""
+    (point_transformer.py:461-465); weight [m, nsample, c / share_planes].
+    Differentiable in feat_v, weight and pos."""
+    require_gpu()
+    if _records((("xyz_q", xyz_q), ("xyz_src", xyz_src)), (feat_v, weight, *pos)):
+        if len(pos) != 6:
+            raise RuntimeError("pos must be (w1, b1, scale_p, shift_p, w2, b2)")
+        return _Aggregate.apply(plan, xyz_q, xyz_src, feat_v, weight, *pos, share_planes)
+    return _aggregate(plan, xyz_q, xyz_src, feat_v, weight, pos, share_planes)[0]
+
+
+def _aggregate(plan, xyz_q, xyz_src, feat_v, weight, pos, share_planes):
     dev, q, s, fv = _plan_inputs(plan, xyz_q, xyz_src, feat_v)
     c, sp = fv.shape[1], int(share_planes)
     if sp < 1 or c % sp:
@@ -197,13 +364,63 @@ def aggregate(plan, xyz_q, xyz_src, feat_v, weight, pos, share_planes):
     out = torch.empty((plan.m, c), dtype=torch.float32, device=dev)
     _lib.call("o3dml_pt_aggregate", ptr(q), ptr(s), ptr(plan.index), ptr(fv), ptr(w), *[ptr(t) for t in p], plan.m,
               plan.k, c, sp, ptr(out), stream_handle(dev))
-    return out
+    return out, (q, s, fv, w, *p)
+
+
+class _Aggregate(torch.autograd.Function):
+    """Saves the forward's inputs only: the softmax is recomputed."""
+
+    @staticmethod
+    def forward(ctx, plan, xyz_q, xyz_src, feat_v, weight, w1, b1, sc, sh, w2, b2, share_planes):
+        out, saved = _aggregate(plan, xyz_q, xyz_src, feat_v, weight, (w1, b1, sc, sh, w2, b2), share_planes)
+        ctx.plan, ctx.share_planes = plan, int(share_planes)
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        plan, sp = ctx.plan, ctx.share_planes
+        q, s, fv, w, w1, b1, sc, sh, w2, b2 = ctx.saved_tensors
+        dev, m, k, c = fv.device, plan.m, plan.k, fv.shape[1]
+        g = to_dev(g, dev, torch.float32)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        dval, dwt, dh, dw2, db2 = new(m, k, c), new(m, k, c // sp), new(m, k, 3), new(c, 3), new(c)
+        ws = _grad_ws(c, dev)
+        _lib.call("o3dml_pt_aggregate_backward", ptr(q), ptr(s), ptr(plan.index), ptr(fv), ptr(w), ptr(w1), ptr(b1),
+                  ptr(sc), ptr(sh), ptr(w2), ptr(b2), ptr(g), m, k, c, sp, ptr(dval), ptr(dwt), ptr(dh), ptr(dw2),
+                  ptr(db2), ptr(ws), ws.numel(), stream_handle(dev))
+        dfv = _gather_sum(plan, dval, c, 0, c) if ctx.needs_input_grad[3] else None
+        first = _pos_hidden_backward(plan, q, s, w1, b1, sc, sh, dh) if any(ctx.needs_input_grad[5:9]) else (None,) * 4
+        return (None, None, None, dfv, dwt, *first, dw2, db2, None)
 
 
 def knn_interpolate(plan, feat):
     """Inverse-distance interpolation (point_transformer.py:737-776): feat
-    [n_src, c] -> [m, c] with weights r / sum r, r = 1 / (distance + 1e-8)."""
+    [n_src, c] -> [m, c] with weights r / sum r, r = 1 / (distance + 1e-8).
+    Differentiable in feat."""
     require_gpu()
+    if _records((), (feat,)):
+        return _Interpolate.apply(plan, feat)
+    return _knn_interpolate(plan, feat)
+
+
+class _Interpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, feat):
+        ctx.plan = plan
+        return _knn_interpolate(plan, feat)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        plan = ctx.plan
+        g = to_dev(g, plan.index.device, torch.float32)
+        c = g.shape[1]
+        return None, _gather_sum(plan, g, c, 0, c, div=plan.k, dist=plan.distance)
+
+
+def _knn_interpolate(plan, feat):
     if not isinstance(plan, Neighbours):
         raise RuntimeError(f"plan must be a Neighbours, got {type(plan)}")
     if plan.distance is None:
@@ -223,7 +440,30 @@ def knn_interpolate(plan, feat):
 
 def group(plan, xyz_q, xyz_src, feat):
     """[xyz_src[idx] - xyz_q[:, None] | feat[idx]] -> [m, nsample, 3 + c]
-    (queryandgroup with use_xyz, point_transformer.py:650-697)."""
+    (queryandgroup with use_xyz, point_transformer.py:650-697).
+    Differentiable in feat."""
+    require_gpu()
+    if _records((("xyz_q", xyz_q), ("xyz_src", xyz_src)), (feat,)):
+        return _Group.apply(plan, xyz_q, xyz_src, feat)
+    return _group(plan, xyz_q, xyz_src, feat)
+
+
+class _Group(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, xyz_q, xyz_src, feat):
+        ctx.plan = plan
+        return _group(plan, xyz_q, xyz_src, feat)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        plan = ctx.plan
+        g = to_dev(g, plan.index.device, torch.float32)
+        c = g.shape[2] - 3
+        return None, None, None, _gather_sum(plan, g, 3 + c, 3, c)
+
+
+def _group(plan, xyz_q, xyz_src, feat):
     dev, q, s, f = _plan_inputs(plan, xyz_q, xyz_src, feat)
     c = f.shape[1]
     out = torch.empty((plan.m, plan.k, 3 + c), dtype=torch.float32, device=dev)
@@ -294,14 +534,14 @@ class Transformer(nn.Module):
         plan = _self_plan(pxo)
         if plan is None:
             plan = Neighbours.from_knn(point, point, self.nsample, row_splits, row_splits)
-        with torch.no_grad():
+        with _graph():
             feat_q, feat_k, feat_v = self.linear_q(feat), self.linear_k(feat), self.linear_v(feat)
             pos = position_encoding(self.linear_p)
             w = relation(plan, point, point, feat_k, feat_q, pos, *fold_bn(self.linear_w[0]))
             # Linear(c, c/s) with the BatchNorm behind it folded in, ReLU, Linear(c/s, c/s)
             scale, shift = fold_bn(self.linear_w[3])
             lin = self.linear_w[2]
-            w = F.relu_(F.linear(w, lin.weight * scale[:, None], lin.bias * scale + shift))
+            w = _relu(F.linear(w, lin.weight * scale[:, None], lin.bias * scale + shift))
             w = self.linear_w[5](w)
             return aggregate(plan, point, point, feat_v, w, pos, self.share_planes)
 
@@ -329,11 +569,11 @@ class TransitionDown(nn.Module):
         if self.training:
             raise NotImplementedError(_TRAINING)
         point, feat, row_splits = pxo[0], pxo[1], pxo[2]
-        with torch.no_grad():
+        with _graph():
             scale, shift = fold_bn(self.bn)
             weight = self.linear.weight * scale[:, None]
             if self.stride == 1:
-                return [point, F.relu_(F.linear(feat, weight, shift)), row_splits]
+                return [point, _relu(F.linear(feat, weight, shift)), row_splits]
             rs = row_splits_host(row_splits, point.shape[0])
             new_rs = np.concatenate([[0], np.cumsum(np.diff(rs) // self.stride)]).astype(np.int64)
             idx = furthest_point_sample_ragged(point, rs, new_rs)
@@ -341,7 +581,7 @@ class TransitionDown(nn.Module):
             new_point = point[idx.long(), :]
             plan = Neighbours.from_knn(point, new_point, self.nsample, rs, new_rs)
             rows = group(plan, new_point, point, feat)  # (m, nsample, 3 + c)
-            feat = F.relu_(F.linear(rows, weight, shift)).max(dim=1).values
+            feat = _relu(F.linear(rows, weight, shift)).max(dim=1).values
             return [new_point, feat, new_rs]
 
 
@@ -365,7 +605,7 @@ class TransitionUp(nn.Module):
     def forward(self, pxo1, pxo2=None):
         if self.training:
             raise NotImplementedError(_TRAINING)
-        with torch.no_grad():
+        with _graph():
             if pxo2 is None:
                 point, feat, row_splits = pxo1[0], pxo1[1], pxo1[2]
                 rs = row_splits_host(row_splits, feat.shape[0])
@@ -400,7 +640,7 @@ class Bottleneck(nn.Module):
         if self.training:
             raise NotImplementedError(_TRAINING)
         point, feat, row_splits = pxo[0], pxo[1], pxo[2]
-        with torch.no_grad():
+        with _graph():
             identity = feat
             feat = self.relu(self.bn1(self.linear1(feat)))
             feat = self.relu(self.bn2(self.transformer2([point, feat, *pxo[2:]])))
@@ -467,7 +707,7 @@ class PointTransformer(nn.Module):
         levels = level_row_splits(_field(batch, "row_splits"), self.strides, self.nsamples)
         if levels[0][-1] != point.shape[0]:
             raise RuntimeError(f"row_splits ends at {int(levels[0][-1])}, point has {point.shape[0]} rows")
-        with torch.no_grad():
+        with _graph():
             if self.in_channels == 3:
                 feat = point
             else:
@@ -496,4 +736,4 @@ class PointTransformer(nn.Module):
 
 __all__ = ["PointTransformer", "Transformer", "TransitionDown", "TransitionUp", "Bottleneck", "Neighbours",
            "furthest_point_sample_ragged", "relation", "aggregate", "knn_interpolate", "group", "level_row_splits",
-           "fold_bn", "position_encoding"]
+           "fold_bn", "position_encoding", "recording_grad"]
