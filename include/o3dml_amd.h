@@ -390,6 +390,23 @@ int o3dml_furthest_point_sampling_ragged(const float* xyz, int64_t n, int64_t B,
                                          const int64_t* new_row_splits, int64_t max_n, int64_t m_total, int32_t* out,
                                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Bucket-pruned farthest-point sampling for large clouds: the results of
+ * o3dml_furthest_point_sampling(_ragged) bit for bit (pointnet2_utils.py:55,
+ * 89-99: greedy from index 0, squared L2, min-distances from 1e10, ties ->
+ * smallest index), the arguments of the ragged form; a dense [B,N,3] call is a
+ * ragged batch with equal splits.  The batch is put in Morton order per cloud
+ * (one radix sort) and cut into buckets of 64 k points, at most 2048 per cloud;
+ * one workgroup per cloud then skips, in each round, every bucket whose box is
+ * no closer to the new sample than the largest min-distance inside it (an
+ * exact fp32 bound: no min-distance of a skipped bucket would have changed).
+ * visited (nullable, device): receives the number of bucket visits of all
+ * clouds and rounds, ceil(n_b / bucket) per cloud in the first round and
+ * whatever the pruning leaves afterwards.  No host read-back. */
+size_t o3dml_fps_pruned_workspace_size(int64_t n, int64_t B, int64_t max_n);
+int o3dml_fps_pruned(const float* xyz, int64_t n, int64_t B, const int64_t* row_splits,
+                     const int64_t* new_row_splits, int64_t max_n, int64_t m_total, int32_t* out, uint64_t* visited,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- PointTransformer inference ops (ml3d/torch/models/point_transformer.py,
  * eval() forward).  Contiguous float32 unless noted; idx int32 [n, nsample]
  * holds source rows in [0, n_src): the kernels trust it (the Python plan

@@ -160,6 +160,9 @@ SIGNATURES = {
     "o3dml_three_interpolate_grad_det": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
     "o3dml_furthest_point_sampling_ragged_workspace_size": (c_sz, [c_i64, c_i64]),
     "o3dml_furthest_point_sampling_ragged": (c_i32, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
+    # fps_pruned.hip
+    "o3dml_fps_pruned_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
+    "o3dml_fps_pruned": (c_i32, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_sz, c_p]),
     # point_transformer.hip
     "o3dml_pt_relation": (c_i32, [c_p] * 13 + [c_i64, c_i64, c_i64, c_p, c_p]),
     "o3dml_pt_aggregate": (c_i32, [c_p] * 11 + [c_i64, c_i64, c_i64, c_i64, c_p, c_p]),

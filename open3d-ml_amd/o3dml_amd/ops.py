@@ -663,16 +663,49 @@ def _check_bn3(name, t):
         raise RuntimeError(f"{name} must be float32 [B, N, 3], got {t.dtype} {list(t.shape)}")
 
 
-def furthest_point_sampling(points, sample_size):
+# "auto" samples a batch whose largest cloud has more points than this through
+# the bucket-pruned kernel (csrc/fps_pruned.hip): the size at which the
+# register variants of csrc/pointnet2.hip end.  DESIGN §5 "Bucket-pruned FPS"
+# has the measurements behind it.
+FPS_PRUNED_ABOVE = 32768
+
+
+def fps_use_pruned(method, max_n):
+    if method not in ("auto", "direct", "pruned"):
+        raise RuntimeError(f"furthest point sampling: method must be 'auto', 'direct' or 'pruned', got {method!r}")
+    return method == "pruned" or (method == "auto" and max_n > FPS_PRUNED_ABOVE)
+
+
+def fps_pruned(x, n, B, rs, nrs, max_n, m_total, dev, want_visited=False):
+    """o3dml_fps_pruned on device points x [n, 3] with host splits -> (int32
+    [m_total] of global rows, the visited-buckets counter or None)."""
+    out = torch.empty(m_total, dtype=torch.int32, device=dev)
+    visited = torch.zeros(1, dtype=torch.int64, device=dev) if want_visited else None
+    ws = workspace(_lib.load().o3dml_fps_pruned_workspace_size(n, B, max_n), dev)
+    _lib.call("o3dml_fps_pruned", ptr(x), n, B, ptr(to_dev(rs, dev)), ptr(to_dev(nrs, dev)), max_n, m_total,
+              ptr(out), ptr(visited) if want_visited else None, ptr(ws), ws.numel(), stream_handle(dev))
+    return out, visited
+
+
+def furthest_point_sampling(points, sample_size, method="auto"):
     """Open3D ``ops.furthest_point_sampling`` (pointnet2_utils.py:55): points
     [B,N,3] -> int32 [B, sample_size]; greedy from index 0, squared L2, ties
-    -> smallest index."""
+    -> smallest index.  method: "direct" (every point in every round),
+    "pruned" (spatial buckets skipped when they cannot change; the same bits)
+    or "auto" (pruned above FPS_PRUNED_ABOVE points per cloud)."""
     dev = gpu_device(points)
     _check_bn3("points", points)
     lib = _lib.load()
     B, N, _ = points.shape
     m = int(sample_size)
     pts = to_dev(points, dev)
+    if fps_use_pruned(method, N) and B > 0 and m > 0 and N > 0:
+        rows = np.arange(B + 1, dtype=np.int64)
+        out, _ = fps_pruned(pts.reshape(B * N, 3), B * N, B, rows * N, rows * m, N, B * m, dev)
+        out = out.view(B, m)
+        if B > 1:  # global rows -> indices inside each cloud
+            out = out - torch.arange(0, B * N, N, dtype=torch.int32, device=dev)[:, None]
+        return back_to(out, points)
     out = torch.empty((B, m), dtype=torch.int32, device=dev)
     ws = workspace(lib.o3dml_furthest_point_sampling_workspace_size(B, N), dev)
     _lib.call("o3dml_furthest_point_sampling", ptr(pts), B, N, m, ptr(out), ptr(ws), ws.numel(), stream_handle(dev))

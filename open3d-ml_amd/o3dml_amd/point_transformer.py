@@ -180,13 +180,16 @@ class Neighbours:
 # ---------------------------------------------------------------------------
 # the ops
 # ---------------------------------------------------------------------------
-def furthest_point_sample_ragged(xyz, row_splits, new_row_splits):
+def furthest_point_sample_ragged(xyz, row_splits, new_row_splits, method="auto", return_visited=False):
     """furthest_point_sample_v2 (pointnet2_utils.py:89-99) in one launch: xyz
     [n, 3], cloud b = rows row_splits[b]..row_splits[b+1], sampled to
     new_row_splits[b+1] - new_row_splits[b] points -> int32 [new_row_splits[-1]]
     of global rows (int32 as in the reference: an int32 tensor plus a 0-dim
     int64 stays int32).  Per cloud the result of ops.furthest_point_sampling
-    on that cloud alone, plus its offset."""
+    on that cloud alone, plus its offset.  method as in
+    ops.furthest_point_sampling ("auto" goes by the largest cloud); with
+    return_visited the result is (rows, int64 [1] device tensor of the bucket
+    visits the pruned kernel made, 0 on the direct path)."""
     dev = gpu_device(xyz)
     x = to_dev(_f32("xyz", xyz, (None, 3)), dev)
     n = x.shape[0]
@@ -201,11 +204,14 @@ def furthest_point_sample_ragged(xyz, row_splits, new_row_splits):
                            "asked of it")
     B, m_total = len(rs) - 1, int(nrs[-1])
     max_n = int(sizes.max()) if B else 0
+    if ops.fps_use_pruned(method, max_n):
+        out, visited = ops.fps_pruned(x, n, B, rs, nrs, max_n, m_total, dev, want_visited=return_visited)
+        return (out, visited) if return_visited else out
     out = torch.empty(m_total, dtype=torch.int32, device=dev)
     ws = workspace(_lib.load().o3dml_furthest_point_sampling_ragged_workspace_size(n, max_n), dev)
     _lib.call("o3dml_furthest_point_sampling_ragged", ptr(x), n, B, ptr(to_dev(rs, dev)), ptr(to_dev(nrs, dev)),
               max_n, m_total, ptr(out), ptr(ws), ws.numel(), stream_handle(dev))
-    return out
+    return (out, torch.zeros(1, dtype=torch.int64, device=dev)) if return_visited else out
 
 
 def fold_bn(bn):
