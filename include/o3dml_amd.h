@@ -513,6 +513,35 @@ int o3dml_pt_aggregate_backward(const float* xyz_q, const float* xyz_src, const 
 int o3dml_roi_pool(const float* xyz, const float* boxes3d, const float* pts_feature, int64_t B, int64_t N, int64_t M,
                    int64_t C, int64_t S, float* pooled, int32_t* empty_flag, int32_t* idx_out, void* stream);
 
+/* ---- fused set abstraction: replaces the grouping, the shared MLP and the
+ * max pooling of a PointNet++ level (ml3d/torch/utils/pointnet/
+ * pointnet2_utils.py QueryAndGroup / GroupAll, then the mlps and max_pool2d of
+ * ml3d/torch/models/utils/pointnet PointnetSAModuleMSG.forward) in one launch.
+ *   xyz      f32 [B,N,3]
+ *   new_xyz  f32 [B,M,3]   or null (no centre is subtracted: GroupAll)
+ *   features f32 [B,N,C]   or null (C = 0)
+ *   idx      i32 [B,M,S]   rows of the same cloud, 0 <= idx < N; or null = identity
+ *                          (then M = 1, S = N: GroupAll)
+ *   use_xyz  row r of group (b,m) = [xyz[b,idx] - new_xyz[b,m] | features[b,idx]]
+ *            (3 + C values), or the features alone (C values) when off
+ *   layers   L in 1..4, widths c_0 = row width, c_1..c_L (host int32 [L+1]);
+ *            layer l: h = relu(W_l h + b_l), W_l [c_l, c_{l-1}], BatchNorm
+ *            already folded in, every layer followed by ReLU
+ *   out      f32 [B,M,c_L] = max over the S rows of the last layer's output
+ * packed (device, packed_len floats = o3dml_sa_mlp_max_packed_size, -1 when a
+ * limit is exceeded): layer after layer W_l transposed [kpad_l][cpad_l]
+ * row-major, then b_l [cpad_l]; kpad_l = c_{l-1} rounded up to 8, cpad_l = c_l
+ * rounded up to 32, the padding zeros.  The subtraction is one rounded f32
+ * subtraction, the products exact f32 accumulated in f32.  Every output
+ * element is written (no memset needed); no atomics; run-to-run bitwise equal.
+ * Inputs are finite; an index outside [0, N) is clamped into the cloud.
+ * Limits (status before any launch): S >= 1, c_0 <= 1027, c_l <= 512,
+ * B * N and B * M below 2^31.  No workspace. */
+int64_t o3dml_sa_mlp_max_packed_size(int n_layers, const int32_t* widths);
+int o3dml_sa_mlp_max(const float* xyz, const float* new_xyz, const float* features, const int32_t* idx, int64_t B,
+                     int64_t N, int64_t M, int64_t S, int64_t C, int use_xyz, int n_layers, const int32_t* widths,
+                     const float* packed, int64_t packed_len, float* out, void* stream);
+
 /* ---- rotated BEV NMS: replaces open3d.ml.torch.ops.nms
  * (ml3d/torch/utils/objdet_helper.py:27, called by multiclass_nms :346 from
  * point_pillars.py:1005).  boxes f32 [N,5] (x1,y1,x2,y2,yaw), scores f32 [N];

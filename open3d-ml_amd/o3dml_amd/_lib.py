@@ -177,6 +177,10 @@ SIGNATURES = {
     "o3dml_pt_aggregate_backward": (c_i32, [c_p] * 12 + [c_i64, c_i64, c_i64, c_i64] + [c_p] * 6 + [c_sz, c_p]),
     # roi_pool.hip
     "o3dml_roi_pool": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    # sa_mlp_max.hip
+    "o3dml_sa_mlp_max_packed_size": (c_i64, [c_i32, c_p]),
+    "o3dml_sa_mlp_max": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_p, c_p, c_i64,
+                                 c_p, c_p]),
     "o3dml_nms_workspace_size": (c_sz, [c_i64]),
     "o3dml_nms": (c_i32, [c_p, c_p, c_i64, c_f32, c_p, c_p, c_p, c_sz, c_p]),
     # box_iou.hip, box_iou_host.cpp

@@ -930,6 +930,112 @@ def roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num):
 
 
 # ---------------------------------------------------------------------------
+# fused set abstraction (PointNet++ level: group, shared MLP, max)
+# ---------------------------------------------------------------------------
+SA_MLP_MAX_LAYERS = 4
+SA_MLP_MAX_WIDTH = 512  # c_1 .. c_L
+SA_MLP_MAX_IN = 1027    # c_0
+
+
+def sa_mlp_widths(weights, biases):
+    """[c_0, .., c_L] of a chain weights[l] float32 [c_l, c_{l-1}], biases[l]
+    float32 [c_l]; RuntimeError when it is no chain or outside the kernel's
+    limits (csrc/sa_mlp_max.hip)."""
+    weights, biases = list(weights), list(biases)
+    if not 1 <= len(weights) <= SA_MLP_MAX_LAYERS or len(biases) != len(weights):
+        raise RuntimeError(f"sa_mlp_max: 1..{SA_MLP_MAX_LAYERS} layers with one bias each, got {len(weights)} weights "
+                           f"and {len(biases)} biases")
+    widths = []
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        for name, t, dim in (("weights", w, 2), ("biases", b, 1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != dim:
+                raise RuntimeError(f"sa_mlp_max: {name}[{l}] must be float32 with {dim} dimensions, got "
+                                   f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+        if b.shape[0] != w.shape[0] or (widths and w.shape[1] != widths[-1]):
+            raise RuntimeError(f"sa_mlp_max: weights[{l}] {list(w.shape)} does not continue the chain "
+                               f"(input width {widths[-1] if widths else w.shape[1]}, bias {list(b.shape)})")
+        if not widths:
+            widths.append(w.shape[1])
+        widths.append(w.shape[0])
+    if not 1 <= widths[0] <= SA_MLP_MAX_IN or not all(1 <= c <= SA_MLP_MAX_WIDTH for c in widths[1:]):
+        raise RuntimeError(f"sa_mlp_max: widths {widths} exceed the limits c_0 <= {SA_MLP_MAX_IN}, "
+                           f"c_l <= {SA_MLP_MAX_WIDTH}")
+    return widths
+
+
+def sa_mlp_pack(weights, biases):
+    """The kernel's weight buffer, float32 1-D on the weights' device: layer
+    after layer W_l transposed to [in, out] with `in` zero-padded to a multiple
+    of 8 and `out` to a multiple of 32, then b_l zero-padded likewise.  Pure
+    torch: needs no GPU."""
+    sa_mlp_widths(weights, biases)
+    parts = []
+    for w, b in zip(weights, biases):
+        cout, cin = w.shape
+        po, pi = -cout % 32, -cin % 8
+        parts.append(torch.nn.functional.pad(w.detach().t(), (0, po, 0, pi)).reshape(-1))
+        parts.append(torch.nn.functional.pad(b.detach(), (0, po)))
+    return torch.cat(parts)
+
+
+def sa_mlp_max(xyz, new_xyz, features, idx, weights, biases, use_xyz=True, packed=None):
+    """A PointNet++ set-abstraction level in one kernel (csrc/sa_mlp_max.hip):
+    xyz [B,N,3], new_xyz [B,M,3] or None (no centre subtracted), features
+    [B,N,C] or None, idx int32 [B,M,S] (rows of the same cloud, as ball_query
+    gives them) or None (one group of all N points: GroupAll) -> float32
+    [B,M,c_L], the maximum over a group's S rows [xyz - centre | features]
+    (the features alone with use_xyz off) pushed through relu(W_l h + b_l) for
+    every layer.  weights[l] is [c_l, c_{l-1}], biases[l] [c_l], BatchNorm
+    folded in by the caller.  `packed` takes sa_mlp_pack(weights, biases) from
+    a caller that keeps it between calls.  Not an Open3D name."""
+    widths = sa_mlp_widths(weights, biases)
+    for name, t, last in (("xyz", xyz, 3), ("new_xyz", new_xyz, 3), ("features", features, None)):
+        if t is None and name != "xyz":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or (
+                last is not None and t.shape[2] != last):
+            raise RuntimeError(f"sa_mlp_max: {name} must be float32 [B, *, {'C' if last is None else last}], got "
+                               f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"sa_mlp_max: {name} must be contiguous")
+    B, N, _ = xyz.shape
+    C = 0 if features is None else features.shape[2]
+    if features is not None and tuple(features.shape[:2]) != (B, N):
+        raise RuntimeError(f"sa_mlp_max: xyz {list(xyz.shape)} and features {list(features.shape)} do not share B and N")
+    if idx is None:
+        M, S = 1, N
+    else:
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.dim() != 3 or idx.shape[0] != B:
+            raise RuntimeError(f"sa_mlp_max: idx must be int32 [{B}, M, S], got {getattr(idx, 'dtype', type(idx))} "
+                               f"{list(getattr(idx, 'shape', []))}")
+        if not idx.is_contiguous():
+            raise RuntimeError("sa_mlp_max: idx must be contiguous")
+        M, S = idx.shape[1], idx.shape[2]
+    if new_xyz is not None and tuple(new_xyz.shape[:2]) != (B, M):
+        raise RuntimeError(f"sa_mlp_max: new_xyz {list(new_xyz.shape)} must be [{B}, {M}, 3]")
+    if S < 1:
+        raise RuntimeError(f"sa_mlp_max: a group needs at least one row, got S = {S}")
+    if not use_xyz and C == 0:
+        raise RuntimeError("sa_mlp_max: no features and use_xyz is off")
+    if widths[0] != (3 if use_xyz else 0) + C:
+        raise RuntimeError(f"sa_mlp_max: weights[0] takes {widths[0]} values, a row has {(3 if use_xyz else 0) + C}")
+    dev = gpu_device(xyz, new_xyz, features, idx)
+    if packed is None:
+        packed = sa_mlp_pack(weights, biases)
+    packed = to_dev(packed, dev)
+    x = to_dev(xyz.detach(), dev)
+    c = None if new_xyz is None else to_dev(new_xyz.detach(), dev)
+    f = None if features is None else to_dev(features.detach(), dev)
+    i = None if idx is None else to_dev(idx, dev)
+    out = torch.empty((B, M, widths[-1]), dtype=torch.float32, device=dev)
+    if B * M:
+        wd = np.asarray(widths, np.int32)
+        _lib.call("o3dml_sa_mlp_max", ptr(x), ptr(c), ptr(f), ptr(i), B, N, M, S, C, int(bool(use_xyz)),
+                  len(widths) - 1, wd.ctypes.data, ptr(packed), packed.numel(), ptr(out), stream_handle(dev))
+    return back_to(out, xyz)
+
+
+# ---------------------------------------------------------------------------
 from .sparse_conv import sparse_conv, sparse_conv_transpose  # noqa: E402,F401
 
 

@@ -4,10 +4,13 @@ forward for mode "RPN" and mode "RCNN".
 
 Through this library's HIP kernels run the farthest-point sampling, the ball
 queries, three_nn / three_interpolate of the feature propagation, the rotated
-BEV NMS of both proposal layers and roi_pool (csrc/roi_pool.hip).  The grouping
-of a set-abstraction level is a plain torch row gather of [xyz | feature] rows
-by the ball-query index (one index_select per scale); the pooled rows of
-roi_pool arrive channels-last already.
+BEV NMS of both proposal layers, roi_pool (csrc/roi_pool.hip) and the set-
+abstraction levels: grouping, shared MLP and max of a scale are one kernel
+(ops.sa_mlp_max, csrc/sa_mlp_max.hip) handed the ball-query index.  With a
+module's `fused` flag off, or for an MLP the kernel does not take, a level is
+the composition it replaces: a torch row gather of [xyz | feature] rows by the
+index, the folded Linears and a max.  The pooled rows of roi_pool arrive
+channels-last already.
 
 Activations are kept channels-last ([B, n, C], [B, n, nsample, C]) from the
 input to the heads, so every 1x1 Conv1d / Conv2d of the reference is a Linear
@@ -73,6 +76,35 @@ def run_channels_last(seq, x):
 # ---------------------------------------------------------------------------
 # PointNet++ modules (pointnet.py, pointnet2_utils.py)
 # ---------------------------------------------------------------------------
+def fused_chain(seq):
+    """(weights, biases) of a Sequential that is a chain of 1x1 Conv ->
+    [BatchNorm] -> ReLU within the limits of ops.sa_mlp_max, the BatchNorm
+    folded in as run_channels_last folds it; None for anything else."""
+    mods, weights, biases = list(seq), [], []
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if not isinstance(m, (nn.Conv1d, nn.Conv2d)) or any(k != 1 for k in m.kernel_size):
+            return None
+        w, b = m.weight.view(m.out_channels, m.in_channels), m.bias
+        i += 1
+        if i < len(mods) and isinstance(mods[i], (nn.BatchNorm1d, nn.BatchNorm2d)):
+            scale, shift = fold_bn(mods[i])
+            w = w * scale[:, None]
+            b = shift if b is None else b * scale + shift
+            i += 1
+        if i >= len(mods) or not isinstance(mods[i], nn.ReLU):
+            return None
+        i += 1
+        weights.append(w.contiguous())
+        biases.append(torch.zeros_like(w[:, 0]) if b is None else b)
+    widths = [w.shape[0] for w in weights]
+    if not 1 <= len(weights) <= ops.SA_MLP_MAX_LAYERS or max(widths) > ops.SA_MLP_MAX_WIDTH or \
+            weights[0].shape[1] > ops.SA_MLP_MAX_IN:
+        return None
+    return weights, biases
+
+
 class QueryAndGroup(nn.Module):
     """Rows [xyz - centre | feature] of the first nsample points inside the
     ball of every centre (pointnet2_utils.py:223-278), channels-last."""
@@ -112,7 +144,10 @@ class PointnetSAModuleMSG(nn.Module):
     """Set abstraction with multi-scale grouping (pointnet.py:110-211).
     forward(xyz [B,N,3], features [B,N,C] or None) -> (new_xyz [B,npoint,3] or
     None, new_features [B, npoint or 1, sum of the scales' widths]); `sampled`
-    holds the FPS rows of the last forward."""
+    holds the FPS rows of the last forward.  `fused` (on by default): a scale
+    whose MLP is a chain of at most four Conv -> [BatchNorm] -> ReLU runs as
+    ops.sa_mlp_max on the ball-query index; off, every scale is composed from
+    torch ops.  The flag is no parameter or buffer."""
 
     def __init__(self, *, npoint, radii, nsamples, mlps, batch_norm=None, use_xyz=True, bias=False):
         super().__init__()
@@ -127,6 +162,20 @@ class PointnetSAModuleMSG(nn.Module):
                 spec[0] += 3
             self.mlps.append(gen_CNN(spec, conv=nn.Conv2d, batch_norm=batch_norm, bias=bias))
         self.sampled = None
+        self.fused = True
+        self._packed = {}  # scale -> (versions of the MLP's tensors, folded weights, biases, packed buffer)
+
+    def _chain(self, k):
+        """The folded chain of scale k and its packed buffer, rebuilt when one
+        of the MLP's tensors was replaced or written to; None when the MLP is
+        not one the kernel takes."""
+        mlp = self.mlps[k]
+        key = tuple((t.data_ptr(), t._version) for t in list(mlp.parameters()) + list(mlp.buffers()))
+        hit = self._packed.get(k)
+        if hit is None or hit[0] != key:
+            chain = fused_chain(mlp)
+            hit = self._packed[k] = (key, None) if chain is None else (key, *chain, ops.sa_mlp_pack(*chain))
+        return hit[1:] if hit[1] is not None else None
 
     def forward(self, xyz, features=None):
         if self.training:
@@ -135,8 +184,21 @@ class PointnetSAModuleMSG(nn.Module):
         if self.npoint is not None:
             self.sampled = ops.furthest_point_sampling(xyz, self.npoint)
             new_xyz = torch.gather(xyz, 1, self.sampled.long().unsqueeze(2).expand(-1, -1, 3))
-        out = [run_channels_last(mlp, grouper(xyz, new_xyz, features)).max(dim=2).values
-               for grouper, mlp in zip(self.groupers, self.mlps)]
+        out = []
+        for k, (grouper, mlp) in enumerate(zip(self.groupers, self.mlps)):
+            chain = self._chain(k) if self.fused else None
+            if chain is None:
+                out.append(run_channels_last(mlp, grouper(xyz, new_xyz, features)).max(dim=2).values)
+                continue
+            weights, biases, packed = chain
+            idx = None
+            if isinstance(grouper, QueryAndGroup):
+                if features is None and not grouper.use_xyz:
+                    raise RuntimeError("QueryAndGroup: no features and use_xyz is off")
+                idx = ops.ball_query(xyz, new_xyz, grouper.radius, grouper.nsample)
+            out.append(ops.sa_mlp_max(xyz.contiguous(), None if idx is None else new_xyz,
+                                      None if features is None else features.contiguous(), idx, weights, biases,
+                                      use_xyz=grouper.use_xyz or features is None, packed=packed))
         return new_xyz, torch.cat(out, dim=2)
 
 
@@ -547,4 +609,5 @@ class PointRCNN(nn.Module):
 
 __all__ = ["PointRCNN", "RPN", "RCNN", "ProposalLayer", "Pointnet2MSG", "PointnetSAModuleMSG", "PointnetSAModule",
            "PointnetFPModule", "QueryAndGroup", "GroupAll", "decode_bbox_target", "enlarge_box3d",
-           "canonical_transform", "rotate_pc_along_y_torch", "xywhr_to_xyxyr", "gen_CNN", "run_channels_last"]
+           "canonical_transform", "rotate_pc_along_y_torch", "xywhr_to_xyxyr", "gen_CNN", "run_channels_last",
+           "fused_chain"]

@@ -11,9 +11,25 @@ warm-up of every shape):
                        bytes (the pooled rows written, the cloud and its
                        features read once) over its time, as GB/s and as a
                        fraction of the 8 TB/s HBM peak;
+  sa_levels            ops.sa_mlp_max at the eleven level / scale shapes of the
+                       yml (RPN: one cloud of 16384 points; RCNN: 100 rois of
+                       512 points), index from this library's FPS and ball
+                       query, beside the composition it replaces on the same
+                       index (row gather, folded Linears + ReLU, max),
+                       alternating after a warm-up of each; the kernel's own
+                       time (timing counter sa_mlp_max); FLOPs and algorithmic
+                       bytes (cloud, index, centres, weights read once, the
+                       output written) from the shape, and the least time the
+                       hardware could take (FLOPs over the 157.3 TF/s f32
+                       matrix peak or bytes over the 8 TB/s HBM peak,
+                       whichever is larger and named in `bound`) over the
+                       kernel time;
   frame_forward_ms     the eval() forward (mode "RCNN") plus get_bboxes of the
                        yml's model on one frame of --points points (default
-                       16384), weights from tests/golden/prcnn_weights.py;
+                       16384), weights from tests/golden/prcnn_weights.py, with
+                       the fused set abstraction; frame_forward_composed_ms the
+                       same with every level's `fused` flag off, the two
+                       alternating in one loop, each with its [min, max];
   frame_ops_ms         per forward, the time inside this library's ops (each
                        call bracketed by device synchronises, so the sum is an
                        upper bound of their share) and the calls.
@@ -38,6 +54,7 @@ sys.path.insert(0, os.path.join(ROOT, "open3d-ml_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 HBM_PEAK = 8.0e12
+MFMA_F32_PEAK = 157.3e12  # dense f32 matrix rate of one MI355X
 OPS = ["furthest_point_sampling", "ball_query", "three_nn", "three_interpolate", "nms", "roi_pool_indexed"]
 
 
@@ -71,6 +88,85 @@ def composed_roi_pool(xyz, boxes, feat, S):
     rows = torch.cat([xyz, feat], dim=2)
     pooled = torch.stack([rows[b][idx[b]] for b in range(B)]) * (cnt > 0).unsqueeze(-1)
     return pooled, (cnt.squeeze(-1) == 0).int(), torch.where(cnt > 0, idx, -1).int()
+
+
+def sa_levels(cfg, dev, rng, iters):
+    """One entry per level and scale of the yml's RPN backbone and RCNN head."""
+    from o3dml_amd import _lib, ops, point_rcnn
+    import torch.nn as nn
+    shapes = []
+    sa = cfg["rpn"]["backbone"]["SA_config"]
+    n_in, c_in = 16384, cfg["rpn"]["backbone"]["in_channels"]
+    for k, m in enumerate([4096, 1024, 256, 64]):
+        for radius, S, mlp in zip(sa["radius"][k], sa["nsample"][k], sa["mlps"][k]):
+            shapes.append((f"rpn{k + 1}_r{radius}", 1, n_in, m, S, c_in, radius, list(mlp), True))
+        n_in, c_in = m, sum(mlp[-1] for mlp in sa["mlps"][k])
+    sa = cfg["rcnn"]["SA_config"]
+    n_in, c_in = 512, cfg["rcnn"]["in_channels"]
+    for k, m in enumerate(sa["npoints"]):
+        shapes.append((f"rcnn{k + 1}", 100, n_in, m, sa["nsample"][k], c_in, sa["radius"][k], list(sa["mlps"][k]),
+                       False))
+        n_in, c_in = m, sa["mlps"][k][-1]
+    lib = _lib.load()
+    out = []
+    for name, B, N, M, S, C, radius, mlp, bn in shapes:
+        widths = [C + 3] + mlp
+        if B == 1:
+            xyz = torch.from_numpy(frame(16384, rng)[None, :N].copy()).to(dev)
+        else:  # a roi's points in its canonical frame
+            xyz = torch.from_numpy(((rng.random((B, N, 3)) - 0.5) * [4.0, 2.0, 6.0]).astype(np.float32)).to(dev)
+        feat = torch.from_numpy(rng.standard_normal((B, N, C)).astype(np.float32)).to(dev) if C else None
+        seq = point_rcnn.gen_CNN(widths, conv=nn.Conv2d, batch_norm=nn.BatchNorm2d if bn else None,
+                                 bias=not bn).to(dev).eval()
+        with torch.no_grad():
+            if M == -1:  # GroupAll
+                M, S, new_xyz, idx = 1, N, None, None
+                rows = torch.arange(B * N, device=dev)
+            else:
+                fps = ops.furthest_point_sampling(xyz, M)
+                new_xyz = torch.gather(xyz, 1, fps.long().unsqueeze(2).expand(-1, -1, 3))
+                idx = ops.ball_query(xyz, new_xyz, radius, S)
+                rows = (idx.long() + (torch.arange(B, device=dev) * N).view(B, 1, 1)).view(-1)
+            weights, biases = point_rcnn.fused_chain(seq)
+            packed = ops.sa_mlp_pack(weights, biases)
+
+            def fused():
+                return ops.sa_mlp_max(xyz, new_xyz, feat, idx, weights, biases, packed=packed)
+
+            def composed():
+                g = xyz.reshape(B * N, 3)[rows].view(B, M, S, 3)
+                if new_xyz is not None:
+                    g = g - new_xyz.unsqueeze(2)
+                if feat is not None:
+                    g = torch.cat([g, feat.reshape(B * N, C)[rows].view(B, M, S, C)], dim=3)
+                return point_rcnn.run_channels_last(seq, g).max(dim=2).values
+
+            a, b = fused(), composed()
+            err = float((a - b).abs().max() / b.abs().max())
+            fused(), composed()
+            tf, tc = [], []
+            for _ in range(iters):
+                tf.append(clock(fused))
+                tc.append(clock(composed))
+            lib.o3dml_timing_enable(1)
+            lib.o3dml_timing_reset()
+            for _ in range(iters):
+                fused()
+            torch.cuda.synchronize()
+            ms, cnt = _lib.kernel_times(["sa_mlp_max"])["sa_mlp_max"]
+            lib.o3dml_timing_enable(0)
+        kernel_ms = ms / max(cnt, 1)
+        flops = 2 * B * M * S * sum(i * o for i, o in zip(widths[:-1], widths[1:]))
+        nbytes = 4 * (B * N * (3 + C) + (0 if idx is None else B * M * S + 3 * B * M) + packed.numel() +
+                      B * M * widths[-1])
+        t_flop, t_byte = flops / MFMA_F32_PEAK, nbytes / HBM_PEAK
+        out.append({"level": name, "shape": [B, N, M, S], "widths": widths,
+                    "fused_ms": round(statistics.median(tf), 4), "kernel_ms": round(kernel_ms, 4),
+                    "composed_ms": round(statistics.median(tc), 4), "max_rel_diff": err, "flops": flops,
+                    "algorithmic_bytes": nbytes, "bound": "matrix" if t_flop >= t_byte else "hbm",
+                    "fraction_of_matrix_peak": round(t_flop / (kernel_ms * 1e-3), 4),
+                    "fraction_of_hbm_peak": round(t_byte / (kernel_ms * 1e-3), 4)})
+    return out
 
 
 def frame(points, rng):
@@ -140,8 +236,25 @@ def main():
     model = model.to(dev).eval()
     cloud = torch.from_numpy(frame(args.points, rng)[None]).to(dev)
     run = lambda: model.get_bboxes(model(cloud))  # noqa: E731
-    run()
-    res["frame_forward_ms"] = round(statistics.median(clock(run) for _ in range(args.iters)), 3)
+    res["sa_levels"] = sa_levels(cfg, dev, rng, args.iters)
+    levels = [m for m in model.modules() if isinstance(m, point_rcnn.PointnetSAModuleMSG)]
+
+    def switch(on):
+        for m in levels:
+            m.fused = on
+
+    times = {True: [], False: []}
+    for on in (True, False):
+        switch(on)
+        run()
+    for _ in range(args.iters):
+        for on in (True, False):
+            switch(on)
+            times[on].append(clock(run))
+    switch(True)
+    for on, key in ((True, "frame_forward_ms"), (False, "frame_forward_composed_ms")):
+        res[key] = round(statistics.median(times[on]), 3)
+        res[key.replace("_ms", "_min_max_ms")] = [round(min(times[on]), 3), round(max(times[on]), 3)]
     spent = {k: [0.0, 0] for k in OPS}
     real = {k: getattr(ops, k) for k in OPS}
 
