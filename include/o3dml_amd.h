@@ -542,6 +542,30 @@ int o3dml_sa_mlp_max(const float* xyz, const float* new_xyz, const float* featur
                      int64_t N, int64_t M, int64_t S, int64_t C, int use_xyz, int n_layers, const int32_t* widths,
                      const float* packed, int64_t packed_len, float* out, void* stream);
 
+/* ---- fused feature propagation: replaces the interpolation, the skip
+ * concatenation and the shared MLP of PointnetFPModule.forward
+ * (ml3d/torch/modules/pointnet.py:252-298) in one launch; three_nn stays
+ * o3dml_three_nn.
+ *   known_feats   f32 [B,m,C2]   C2 >= 1
+ *   unknown_feats f32 [B,n,C1]   or null (C1 = 0)
+ *   dist2, idx    f32 / i32 [B,n,3] as o3dml_three_nn writes them (+inf and
+ *                 index 0 in a slot no known point filled)
+ *   layers        as o3dml_sa_mlp_max: L in 1..4, widths host int32 [L+1],
+ *                 c_0 = C2 + C1, every layer relu(W_l h + b_l)
+ *   out           f32 [B,n,c_L]
+ * Row i of item b = [ sum_j w_j known_feats[b, idx[b,i,j]] | unknown_feats[b,i] ],
+ * r_j = 1 / (sqrt(dist2_j) + 1e-8), w_j = r_j / (r_0 + r_1 + r_2) in IEEE f32: a
+ * +inf slot weighs exactly 0.  packed: the layout of o3dml_sa_mlp_max, sized by
+ * o3dml_fp_mlp_packed_size (-1 when a limit is exceeded).  Products exact f32
+ * accumulated in f32, bias last.  Every output element is written (no memset
+ * needed); no atomics; run-to-run bitwise equal.  Features are finite; an
+ * index outside [0, m) is clamped.  Limits (status before any launch):
+ * c_0 <= 2048, c_l <= 512, B * n and B * m below 2^31.  No workspace. */
+int64_t o3dml_fp_mlp_packed_size(int n_layers, const int32_t* widths);
+int o3dml_fp_mlp(const float* known_feats, const float* unknown_feats, const float* dist2, const int32_t* idx,
+                 int64_t B, int64_t n, int64_t m, int64_t C2, int64_t C1, int n_layers, const int32_t* widths,
+                 const float* packed, int64_t packed_len, float* out, void* stream);
+
 /* ---- rotated BEV NMS: replaces open3d.ml.torch.ops.nms
  * (ml3d/torch/utils/objdet_helper.py:27, called by multiclass_nms :346 from
  * point_pillars.py:1005).  boxes f32 [N,5] (x1,y1,x2,y2,yaw), scores f32 [N];

@@ -935,40 +935,44 @@ def roi_pool(xyz, boxes3d, pts_feature, sampled_pts_num):
 SA_MLP_MAX_LAYERS = 4
 SA_MLP_MAX_WIDTH = 512  # c_1 .. c_L
 SA_MLP_MAX_IN = 1027    # c_0
+FP_MLP_LAYERS = 4
+FP_MLP_WIDTH = 512      # c_1 .. c_L
+FP_MLP_IN = 2048        # c_0 = C2 + C1
 
 
-def sa_mlp_widths(weights, biases):
+def sa_mlp_widths(weights, biases, max_in=SA_MLP_MAX_IN, op="sa_mlp_max"):
     """[c_0, .., c_L] of a chain weights[l] float32 [c_l, c_{l-1}], biases[l]
     float32 [c_l]; RuntimeError when it is no chain or outside the kernel's
-    limits (csrc/sa_mlp_max.hip)."""
+    limits (csrc/sa_mlp_max.hip; csrc/fp_mlp.hip with its own bound on c_0)."""
     weights, biases = list(weights), list(biases)
     if not 1 <= len(weights) <= SA_MLP_MAX_LAYERS or len(biases) != len(weights):
-        raise RuntimeError(f"sa_mlp_max: 1..{SA_MLP_MAX_LAYERS} layers with one bias each, got {len(weights)} weights "
+        raise RuntimeError(f"{op}: 1..{SA_MLP_MAX_LAYERS} layers with one bias each, got {len(weights)} weights "
                            f"and {len(biases)} biases")
     widths = []
     for l, (w, b) in enumerate(zip(weights, biases)):
         for name, t, dim in (("weights", w, 2), ("biases", b, 1)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != dim:
-                raise RuntimeError(f"sa_mlp_max: {name}[{l}] must be float32 with {dim} dimensions, got "
+                raise RuntimeError(f"{op}: {name}[{l}] must be float32 with {dim} dimensions, got "
                                    f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
         if b.shape[0] != w.shape[0] or (widths and w.shape[1] != widths[-1]):
-            raise RuntimeError(f"sa_mlp_max: weights[{l}] {list(w.shape)} does not continue the chain "
+            raise RuntimeError(f"{op}: weights[{l}] {list(w.shape)} does not continue the chain "
                                f"(input width {widths[-1] if widths else w.shape[1]}, bias {list(b.shape)})")
         if not widths:
             widths.append(w.shape[1])
         widths.append(w.shape[0])
-    if not 1 <= widths[0] <= SA_MLP_MAX_IN or not all(1 <= c <= SA_MLP_MAX_WIDTH for c in widths[1:]):
-        raise RuntimeError(f"sa_mlp_max: widths {widths} exceed the limits c_0 <= {SA_MLP_MAX_IN}, "
+    if not 1 <= widths[0] <= max_in or not all(1 <= c <= SA_MLP_MAX_WIDTH for c in widths[1:]):
+        raise RuntimeError(f"{op}: widths {widths} exceed the limits c_0 <= {max_in}, "
                            f"c_l <= {SA_MLP_MAX_WIDTH}")
     return widths
 
 
-def sa_mlp_pack(weights, biases):
+def sa_mlp_pack(weights, biases, max_in=SA_MLP_MAX_IN, op="sa_mlp_max"):
     """The kernel's weight buffer, float32 1-D on the weights' device: layer
     after layer W_l transposed to [in, out] with `in` zero-padded to a multiple
     of 8 and `out` to a multiple of 32, then b_l zero-padded likewise.  Pure
-    torch: needs no GPU."""
-    sa_mlp_widths(weights, biases)
+    torch: needs no GPU.  fp_mlp takes the same buffer: pack for it with
+    max_in=FP_MLP_IN."""
+    sa_mlp_widths(weights, biases, max_in, op)
     parts = []
     for w, b in zip(weights, biases):
         cout, cin = w.shape
@@ -1033,6 +1037,58 @@ def sa_mlp_max(xyz, new_xyz, features, idx, weights, biases, use_xyz=True, packe
         _lib.call("o3dml_sa_mlp_max", ptr(x), ptr(c), ptr(f), ptr(i), B, N, M, S, C, int(bool(use_xyz)),
                   len(widths) - 1, wd.ctypes.data, ptr(packed), packed.numel(), ptr(out), stream_handle(dev))
     return back_to(out, xyz)
+
+
+# ---------------------------------------------------------------------------
+# fused feature propagation (PointNet++ decoder: interpolate, concatenate, shared MLP)
+# ---------------------------------------------------------------------------
+def fp_mlp(unknown_feats, known_feats, dist2, idx, weights, biases, packed=None):
+    """A PointNet++ feature-propagation module after its three_nn in one kernel
+    (csrc/fp_mlp.hip; pointnet.py:252-298): unknown_feats [B,n,C1] or None,
+    known_feats [B,m,C2], dist2 float32 and idx int32 [B,n,3] as three_nn
+    returns them -> float32 [B,n,c_L]: the rows [sum_j w_j known_feats[idx_j] |
+    unknown_feats] with w_j the normalised 1 / (sqrt(dist2_j) + 1e-8), pushed
+    through relu(W_l h + b_l) for every layer.  weights[l] is [c_l, c_{l-1}],
+    c_0 = C2 + C1, biases[l] [c_l], BatchNorm folded in by the caller.
+    `packed` takes sa_mlp_pack(weights, biases, FP_MLP_IN) from a caller that
+    keeps it between calls.  Not an Open3D name."""
+    widths = sa_mlp_widths(weights, biases, FP_MLP_IN, "fp_mlp")
+    for name, t, dtype, last in (("unknown_feats", unknown_feats, torch.float32, None),
+                                 ("known_feats", known_feats, torch.float32, None),
+                                 ("dist2", dist2, torch.float32, 3), ("idx", idx, torch.int32, 3)):
+        if t is None and name == "unknown_feats":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 3 or (
+                last is not None and t.shape[2] != last):
+            raise RuntimeError(f"fp_mlp: {name} must be {str(dtype)[6:]} [B, *, {'C' if last is None else last}], got "
+                               f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"fp_mlp: {name} must be contiguous")
+    B, n, _ = dist2.shape
+    m, C2 = known_feats.shape[1:]
+    C1 = 0 if unknown_feats is None else unknown_feats.shape[2]
+    if tuple(idx.shape) != (B, n, 3) or known_feats.shape[0] != B or (
+            unknown_feats is not None and tuple(unknown_feats.shape[:2]) != (B, n)):
+        raise RuntimeError(f"fp_mlp: dist2 {list(dist2.shape)}, idx {list(idx.shape)}, known_feats "
+                           f"{list(known_feats.shape)} and unknown_feats "
+                           f"{None if unknown_feats is None else list(unknown_feats.shape)} do not share B and n")
+    if C2 < 1 or (m < 1 and B * n):
+        raise RuntimeError(f"fp_mlp: known_feats {list(known_feats.shape)} must hold at least one point and channel")
+    if widths[0] != C2 + C1:
+        raise RuntimeError(f"fp_mlp: weights[0] takes {widths[0]} values, a row has {C2} + {C1}")
+    dev = gpu_device(known_feats, unknown_feats, dist2, idx)
+    if packed is None:
+        packed = sa_mlp_pack(weights, biases, FP_MLP_IN, "fp_mlp")
+    packed = to_dev(packed, dev)
+    k = to_dev(known_feats.detach(), dev)
+    u = None if unknown_feats is None else to_dev(unknown_feats.detach(), dev)
+    d, i = to_dev(dist2.detach(), dev), to_dev(idx, dev)
+    out = torch.empty((B, n, widths[-1]), dtype=torch.float32, device=dev)
+    if B * n:
+        wd = np.asarray(widths, np.int32)
+        _lib.call("o3dml_fp_mlp", ptr(k), ptr(u), ptr(d), ptr(i), B, n, m, C2, C1, len(widths) - 1, wd.ctypes.data,
+                  ptr(packed), packed.numel(), ptr(out), stream_handle(dev))
+    return back_to(out, known_feats)
 
 
 # ---------------------------------------------------------------------------

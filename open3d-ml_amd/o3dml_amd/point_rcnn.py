@@ -76,10 +76,11 @@ def run_channels_last(seq, x):
 # ---------------------------------------------------------------------------
 # PointNet++ modules (pointnet.py, pointnet2_utils.py)
 # ---------------------------------------------------------------------------
-def fused_chain(seq):
+def fused_chain(seq, max_in=ops.SA_MLP_MAX_IN):
     """(weights, biases) of a Sequential that is a chain of 1x1 Conv ->
-    [BatchNorm] -> ReLU within the limits of ops.sa_mlp_max, the BatchNorm
-    folded in as run_channels_last folds it; None for anything else."""
+    [BatchNorm] -> ReLU within the limits of ops.sa_mlp_max (of ops.fp_mlp
+    with max_in=ops.FP_MLP_IN: the two differ in the bound on c_0 only), the
+    BatchNorm folded in as run_channels_last folds it; None for anything else."""
     mods, weights, biases = list(seq), [], []
     i = 0
     while i < len(mods):
@@ -100,7 +101,7 @@ def fused_chain(seq):
         biases.append(torch.zeros_like(w[:, 0]) if b is None else b)
     widths = [w.shape[0] for w in weights]
     if not 1 <= len(weights) <= ops.SA_MLP_MAX_LAYERS or max(widths) > ops.SA_MLP_MAX_WIDTH or \
-            weights[0].shape[1] > ops.SA_MLP_MAX_IN:
+            weights[0].shape[1] > max_in:
         return None
     return weights, biases
 
@@ -214,16 +215,38 @@ class PointnetFPModule(nn.Module):
     """Feature propagation (pointnet.py:252-298): the known features are
     interpolated over the three nearest known points with inverse-distance
     weights, concatenated with the unknown points' own and passed through the
-    MLP.  Channels-last in and out."""
+    MLP.  Channels-last in and out.  `fused` (on by default): an MLP that is a
+    chain of at most four Conv -> [BatchNorm] -> ReLU within the limits of
+    ops.fp_mlp runs as three_nn and that one kernel; off, the steps are composed
+    from three_interpolate and torch ops.  The flag is no parameter or buffer."""
 
     def __init__(self, *, mlp, batch_norm=None, bias=False):
         super().__init__()
         self.mlp = gen_CNN(mlp, conv=nn.Conv2d, batch_norm=batch_norm, bias=bias)
+        self.fused = True
+        self._packed = None  # (versions of the MLP's tensors, folded weights, biases, packed buffer)
+
+    def _chain(self):
+        """The folded chain and its packed buffer, rebuilt when one of the
+        MLP's tensors was replaced or written to; None when the MLP is not one
+        the kernel takes."""
+        key = tuple((t.data_ptr(), t._version) for t in list(self.mlp.parameters()) + list(self.mlp.buffers()))
+        hit = self._packed
+        if hit is None or hit[0] != key:
+            chain = fused_chain(self.mlp, ops.FP_MLP_IN)
+            hit = self._packed = (key, None) if chain is None else (
+                key, *chain, ops.sa_mlp_pack(*chain, ops.FP_MLP_IN, "fp_mlp"))
+        return hit[1:] if hit[1] is not None else None
 
     def forward(self, unknown, known, unknown_feats, known_feats):
         if self.training:
             raise NotImplementedError(_TRAINING)
         dist2, idx = ops.three_nn(unknown, known)
+        chain = self._chain() if self.fused else None
+        if chain is not None:
+            weights, biases, packed = chain
+            return ops.fp_mlp(None if unknown_feats is None else unknown_feats.contiguous(), known_feats.contiguous(),
+                              dist2, idx, weights, biases, packed=packed)
         recip = 1.0 / (torch.sqrt(dist2) + 1e-8)
         weight = recip / torch.sum(recip, dim=2, keepdim=True)
         interpolated = ops.three_interpolate(known_feats.transpose(1, 2).contiguous(), idx, weight).transpose(1, 2)

@@ -255,6 +255,17 @@ def _(xyz, boxes3d, pts_feature, sampled_pts_num):
     return (xyz.new_empty(bm + (sampled_pts_num, 3 + pts_feature.shape[2])), xyz.new_empty(bm, dtype=torch.int32))
 
 
+@_op("fp_mlp")
+def fp_mlp(unknown_feats: Optional[Tensor], known_feats: Tensor, dist2: Tensor, idx: Tensor, weights: list[Tensor],
+           biases: list[Tensor]) -> Tensor:
+    return ops.fp_mlp(unknown_feats, known_feats, dist2, idx, weights, biases)
+
+
+@fp_mlp.register_fake
+def _(unknown_feats, known_feats, dist2, idx, weights, biases):
+    return known_feats.new_empty((dist2.shape[0], dist2.shape[1], weights[-1].shape[0]))
+
+
 # ----------------------------------------------------------------- sparse convolution
 @_op("sparse_conv")
 def sparse_conv(filters: Tensor, inp_features: Tensor, inp_importance: Optional[Tensor], neighbors_index: Tensor,
@@ -335,4 +346,4 @@ sparse_conv_transpose.register_autograd(_sct_backward, setup_context=_sct_setup)
 OPS = ("build_spatial_hash_table", "fixed_radius_search", "knn_search", "radius_search", "ragged_to_dense",
        "reduce_subarrays_sum", "voxelize", "furthest_point_sampling", "ball_query", "three_nn", "three_interpolate",
        "three_interpolate_grad", "nms", "sparse_conv", "sparse_conv_transpose", "trilinear_devoxelize_forward",
-       "trilinear_devoxelize_backward", "roi_pool")
+       "trilinear_devoxelize_backward", "roi_pool", "fp_mlp")

@@ -24,12 +24,22 @@ warm-up of every shape):
                        matrix peak or bytes over the 8 TB/s HBM peak,
                        whichever is larger and named in `bound`) over the
                        kernel time;
+  fp_modules           ops.fp_mlp at the four feature-propagation shapes of the
+                       yml's RPN backbone (B = 1; dist2 and idx from this
+                       library's three_nn, not timed), beside the composition
+                       it replaces (weights from dist2, three_interpolate on
+                       the transposed features, concatenate, folded Linears +
+                       ReLU), alternating after a warm-up of each; the kernel's
+                       own time (timing counter fp_mlp); FLOPs of the layers
+                       over the f32 matrix peak against the kernel time;
   frame_forward_ms     the eval() forward (mode "RCNN") plus get_bboxes of the
                        yml's model on one frame of --points points (default
                        16384), weights from tests/golden/prcnn_weights.py, with
-                       the fused set abstraction; frame_forward_composed_ms the
-                       same with every level's `fused` flag off, the two
-                       alternating in one loop, each with its [min, max];
+                       the fused set abstraction and feature propagation;
+                       frame_forward_composed_ms the same with every level's
+                       `fused` flag off, frame_forward_fp_composed_ms with
+                       only the feature-propagation modules' flags off, the
+                       three alternating in one loop, each with its [min, max];
   frame_ops_ms         per forward, the time inside this library's ops (each
                        call bracketed by device synchronises, so the sum is an
                        upper bound of their share) and the calls.
@@ -55,7 +65,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 HBM_PEAK = 8.0e12
 MFMA_F32_PEAK = 157.3e12  # dense f32 matrix rate of one MI355X
-OPS = ["furthest_point_sampling", "ball_query", "three_nn", "three_interpolate", "nms", "roi_pool_indexed"]
+OPS = ["furthest_point_sampling", "ball_query", "three_nn", "three_interpolate", "fp_mlp", "sa_mlp_max", "nms",
+       "roi_pool_indexed"]
 
 
 def clock(fn):
@@ -169,6 +180,62 @@ def sa_levels(cfg, dev, rng, iters):
     return out
 
 
+def fp_modules(cfg, dev, rng, iters):
+    """One entry per feature-propagation module of the yml's RPN backbone."""
+    from o3dml_amd import _lib, ops, point_rcnn
+    import torch.nn as nn
+    bb = cfg["rpn"]["backbone"]
+    npts = [16384, 4096, 1024, 256, 64]
+    skip = [bb["in_channels"]] + [sum(m[-1] for m in mlps) for mlps in bb["SA_config"]["mlps"]]
+    fp = [list(m) for m in bb["fp_mlps"]]
+    lib = _lib.load()
+    out = []
+    for k in range(len(fp)):
+        n, m, C1 = npts[k], npts[k + 1], skip[k]
+        C2 = fp[k + 1][-1] if k + 1 < len(fp) else skip[-1]
+        widths = [C2 + C1] + fp[k]
+        cloud = torch.from_numpy(frame(16384, rng)[None]).to(dev)
+        unknown, known = cloud[:, :n].contiguous(), cloud[:, :m].contiguous()
+        kf = torch.from_numpy(rng.standard_normal((1, m, C2)).astype(np.float32)).to(dev)
+        uf = torch.from_numpy(rng.standard_normal((1, n, C1)).astype(np.float32)).to(dev) if C1 else None
+        seq = point_rcnn.gen_CNN(widths, conv=nn.Conv2d, batch_norm=nn.BatchNorm2d, bias=False).to(dev).eval()
+        with torch.no_grad():
+            dist2, idx = ops.three_nn(unknown, known)
+            weights, biases = point_rcnn.fused_chain(seq, ops.FP_MLP_IN)
+            packed = ops.sa_mlp_pack(weights, biases, ops.FP_MLP_IN, "fp_mlp")
+
+            def fused():
+                return ops.fp_mlp(uf, kf, dist2, idx, weights, biases, packed=packed)
+
+            def composed():
+                recip = 1.0 / (torch.sqrt(dist2) + 1e-8)
+                weight = recip / torch.sum(recip, dim=2, keepdim=True)
+                h = ops.three_interpolate(kf.transpose(1, 2).contiguous(), idx, weight).transpose(1, 2)
+                return point_rcnn.run_channels_last(seq, h if uf is None else torch.cat([h, uf], dim=2))
+
+            a, b = fused(), composed()
+            err = float((a - b).abs().max() / b.abs().max())
+            fused(), composed()
+            tf, tc = [], []
+            for _ in range(iters):
+                tf.append(clock(fused))
+                tc.append(clock(composed))
+            lib.o3dml_timing_enable(1)
+            lib.o3dml_timing_reset()
+            for _ in range(iters):
+                fused()
+            torch.cuda.synchronize()
+            ms, cnt = _lib.kernel_times(["fp_mlp"])["fp_mlp"]
+            lib.o3dml_timing_enable(0)
+        kernel_ms = ms / max(cnt, 1)
+        flops = 2 * n * sum(i * o for i, o in zip(widths[:-1], widths[1:]))
+        out.append({"module": f"fp{k + 1}", "shape": [1, n, m, C2, C1], "widths": widths,
+                    "fused_ms": round(statistics.median(tf), 4), "kernel_ms": round(kernel_ms, 4),
+                    "composed_ms": round(statistics.median(tc), 4), "max_rel_diff": err, "flops": flops,
+                    "fraction_of_matrix_peak": round(flops / MFMA_F32_PEAK / (kernel_ms * 1e-3), 4)})
+    return out
+
+
 def frame(points, rng):
     """A synthetic camera-frame cloud: ground clutter over 40 x 70 m and 20
     car-sized blobs holding half of the points."""
@@ -237,22 +304,27 @@ def main():
     cloud = torch.from_numpy(frame(args.points, rng)[None]).to(dev)
     run = lambda: model.get_bboxes(model(cloud))  # noqa: E731
     res["sa_levels"] = sa_levels(cfg, dev, rng, args.iters)
+    res["fp_modules"] = fp_modules(cfg, dev, rng, args.iters)
     levels = [m for m in model.modules() if isinstance(m, point_rcnn.PointnetSAModuleMSG)]
+    props = [m for m in model.modules() if isinstance(m, point_rcnn.PointnetFPModule)]
 
-    def switch(on):
+    def switch(on):  # True: all fused; False: all composed; "fp": only the feature propagation composed
         for m in levels:
-            m.fused = on
+            m.fused = bool(on)
+        for m in props:
+            m.fused = on is True
 
-    times = {True: [], False: []}
-    for on in (True, False):
+    times = {True: [], False: [], "fp": []}
+    for on in times:
         switch(on)
         run()
     for _ in range(args.iters):
-        for on in (True, False):
+        for on in times:
             switch(on)
             times[on].append(clock(run))
     switch(True)
-    for on, key in ((True, "frame_forward_ms"), (False, "frame_forward_composed_ms")):
+    for on, key in ((True, "frame_forward_ms"), (False, "frame_forward_composed_ms"),
+                    ("fp", "frame_forward_fp_composed_ms")):
         res[key] = round(statistics.median(times[on]), 3)
         res[key.replace("_ms", "_min_max_ms")] = [round(min(times[on]), 3), round(max(times[on]), 3)]
     spent = {k: [0.0, 0] for k in OPS}
