@@ -566,6 +566,29 @@ int o3dml_fp_mlp(const float* known_feats, const float* unknown_feats, const flo
                  int64_t B, int64_t n, int64_t m, int64_t C2, int64_t C1, int n_layers, const int32_t* widths,
                  const float* packed, int64_t packed_len, float* out, void* stream);
 
+/* ---- dense voxel convolution: replaces one Conv3d(k = 3, stride 1,
+ * padding 1) -> BatchNorm3d (eval) -> LeakyReLU triple of PVConv's voxel_layers
+ * (ml3d/torch/models/pvcnn.py PVConv: `self.voxel_layers(voxel_features)`) in
+ * one launch.
+ *   grid    f32 [B,Cin,r,r,r]  as o3dml_avg_voxelize_forward writes it
+ *   packed  device, packed_len floats = o3dml_voxel_conv3d_packed_size(Cin, Cout)
+ *           (-1 when a limit is exceeded): the weights tap-major
+ *           [27][kpad][cpad], tap = (dx*3 + dy)*3 + dz, entry = W[co,ci,dx,dy,dz]
+ *           with the BatchNorm folded in, kpad = Cin rounded up to 8, cpad =
+ *           Cout rounded up to 32, then the bias [cpad]; the padding zeros
+ *   out     f32 [B,Cout,r,r,r] = act(bias[co] + sum W[co,ci,dx,dy,dz] *
+ *           grid[b,ci,x+dx-1,y+dy-1,z+dz-1]) (cross-correlation, zeros outside
+ *           the grid); act(v) = v > 0 ? v : v * negative_slope when has_slope,
+ *           else v
+ * Products exact f32 accumulated in f32 in one fixed order of k, bias last.
+ * Every output element is written (no memset needed); no atomics; nothing
+ * accumulated across workgroups; run-to-run bitwise equal.  Inputs are finite.
+ * Limits (status before any launch): r in 1..1290 (r^3 below 2^31), Cin >= 1,
+ * Cout in 1..512, packed_len below 2^31.  No workspace. */
+int64_t o3dml_voxel_conv3d_packed_size(int64_t Cin, int64_t Cout);
+int o3dml_voxel_conv3d(const float* grid, const float* packed, int64_t packed_len, int64_t B, int64_t Cin,
+                       int64_t Cout, int64_t r, int has_slope, float negative_slope, float* out, void* stream);
+
 /* ---- rotated BEV NMS: replaces open3d.ml.torch.ops.nms
  * (ml3d/torch/utils/objdet_helper.py:27, called by multiclass_nms :346 from
  * point_pillars.py:1005).  boxes f32 [N,5] (x1,y1,x2,y2,yaw), scores f32 [N];

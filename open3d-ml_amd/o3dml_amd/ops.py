@@ -1092,6 +1092,90 @@ def fp_mlp(unknown_feats, known_feats, dist2, idx, weights, biases, packed=None)
 
 
 # ---------------------------------------------------------------------------
+# dense voxel convolution (PVConv voxel branch: Conv3d 3x3x3 + folded BatchNorm + LeakyReLU)
+# ---------------------------------------------------------------------------
+VOXEL_CONV3D_COUT = 512
+
+
+def _voxel_conv3d_weight(weight, bias):
+    """(Cout, Cin) of a float32 weight [Cout, Cin, 3, 3, 3] and its bias [Cout]
+    or None; RuntimeError for anything else or a Cout above the kernel's limit."""
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.dim() != 5 or \
+            tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[0] < 1 or weight.shape[1] < 1:
+        raise RuntimeError("voxel_conv3d: weight must be float32 [Cout, Cin, 3, 3, 3], got "
+                           f"{getattr(weight, 'dtype', type(weight))} {list(getattr(weight, 'shape', []))}")
+    cout, cin = weight.shape[:2]
+    if cout > VOXEL_CONV3D_COUT:
+        raise RuntimeError(f"voxel_conv3d: Cout = {cout} exceeds the limit {VOXEL_CONV3D_COUT}")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32
+                             or tuple(bias.shape) != (cout,)):
+        raise RuntimeError(f"voxel_conv3d: bias must be float32 [{cout}], got {getattr(bias, 'dtype', type(bias))} "
+                           f"{list(getattr(bias, 'shape', []))}")
+    return cout, cin
+
+
+def voxel_conv3d_pack(weight, bias=None):
+    """The kernel's weight buffer, float32 1-D on the weight's device: the
+    weight [Cout, Cin, 3, 3, 3] tap-major as [27, kpad, cpad] (tap = (dx*3 +
+    dy)*3 + dz, kpad = Cin rounded up to 8, cpad = Cout rounded up to 32), then
+    the bias [cpad] (zeros when None); the padding is zeros.  Pure torch: needs
+    no GPU."""
+    cout, cin = _voxel_conv3d_weight(weight, bias)
+    po, pi = -cout % 32, -cin % 8
+    w = torch.nn.functional.pad(weight.detach().permute(2, 3, 4, 1, 0).reshape(27, cin, cout), (0, po, 0, pi))
+    b = weight.new_zeros(cout) if bias is None else bias.detach().to(weight.device)
+    return torch.cat([w.reshape(-1), torch.nn.functional.pad(b, (0, po))])
+
+
+def voxel_conv3d(grid, weight, bias=None, negative_slope=None, packed=None, out=None):
+    """Conv3d(Cin, Cout, 3, stride=1, padding=1) on a dense voxel grid with the
+    bias and an optional LeakyReLU in one kernel (csrc/voxel_conv3d.hip; PVConv
+    voxel_layers): grid float32 [B,Cin,r,r,r] contiguous, weight [Cout,Cin,3,3,3]
+    (a BatchNorm folded in by the caller), bias [Cout] or None -> float32
+    [B,Cout,r,r,r] = leaky(conv + bias), or conv + bias when negative_slope is
+    None.  `packed` takes voxel_conv3d_pack(weight, bias) from a caller that
+    keeps it between calls.  `out` takes a contiguous float32 [B,Cout,r,r,r] on
+    the GPU to write into (every element is written) and is returned.  Forward
+    only.  Not an Open3D name."""
+    cout, cin = _voxel_conv3d_weight(weight, bias)
+    if not isinstance(grid, torch.Tensor) or grid.dtype != torch.float32 or grid.dim() != 5 or \
+            len(set(grid.shape[2:])) != 1 or grid.shape[2] < 1:
+        raise RuntimeError("voxel_conv3d: grid must be float32 [B, Cin, r, r, r], got "
+                           f"{getattr(grid, 'dtype', type(grid))} {list(getattr(grid, 'shape', []))}")
+    if not grid.is_contiguous():
+        raise RuntimeError("voxel_conv3d: grid must be contiguous")
+    B, _, r = grid.shape[:3]
+    if grid.shape[1] != cin:
+        raise RuntimeError(f"voxel_conv3d: weight {list(weight.shape)} takes {cin} channels, the grid has "
+                           f"{grid.shape[1]}")
+    if packed is not None:
+        want = 27 * (cin + -cin % 8) * (cout + -cout % 32) + cout + -cout % 32
+        if not isinstance(packed, torch.Tensor) or packed.dtype != torch.float32 or \
+                tuple(packed.shape) != (want,) or not packed.is_contiguous():
+            raise RuntimeError(f"voxel_conv3d: packed must be contiguous float32 [{want}] (voxel_conv3d_pack), got "
+                               f"{getattr(packed, 'dtype', type(packed))} {list(getattr(packed, 'shape', []))}")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
+                            or tuple(out.shape) != (B, cout, r, r, r) or not out.is_contiguous()):
+        raise RuntimeError(f"voxel_conv3d: out must be contiguous float32 [{B}, {cout}, {r}, {r}, {r}] on the GPU, "
+                           f"got {getattr(out, 'dtype', type(out))} {list(getattr(out, 'shape', []))} on "
+                           f"{getattr(out, 'device', None)}")
+    dev = gpu_device(grid, weight, out)
+    if packed is None:
+        packed = voxel_conv3d_pack(weight, bias)
+    packed = to_dev(packed, dev)
+    g = to_dev(grid.detach(), dev)
+    given = out is not None
+    if given and out.device != dev:
+        raise RuntimeError(f"voxel_conv3d: out is on {out.device}, the call runs on {dev}")
+    if not given:
+        out = torch.empty((B, cout, r, r, r), dtype=torch.float32, device=dev)
+    if B:
+        _lib.call("o3dml_voxel_conv3d", ptr(g), ptr(packed), packed.numel(), B, cin, cout, r,
+                  int(negative_slope is not None), float(negative_slope or 0.0), ptr(out), stream_handle(dev))
+    return out if given else back_to(out, grid)
+
+
+# ---------------------------------------------------------------------------
 from .sparse_conv import sparse_conv, sparse_conv_transpose  # noqa: E402,F401
 
 

@@ -12,7 +12,12 @@ has r = 32 once and r = 16 three times) and every block of that resolution
 shares them; the per-voxel lists the devoxelize backward sums over are built
 once per resolution on the first backward.  (a) stays in torch exactly as the
 reference writes it: one ulp there moves points across voxel boundaries.
-Conv3d and BatchNorm3d stay torch / MIOpen.
+(c): in eval() without recorded gradients each Conv3d + BatchNorm3d +
+LeakyReLU triple of a block's voxel_layers is one ops.voxel_conv3d call
+(csrc/voxel_conv3d.hip: implicit GEMM on the f32 MFMA, BatchNorm folded from
+the running statistics), switched by PVConv.fused; in training, with recorded
+gradients or for another layer pattern Conv3d and BatchNorm3d stay torch /
+MIOpen.
 
 Every sum in the HIP ops runs in one fixed order (no float atomics): the
 point <-> voxel transfers are bitwise reproducible, forward and backward.
@@ -25,8 +30,9 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, ops
 from ._util import gpu_device, ptr, stream_handle, to_dev, workspace
+from .point_transformer import fold_bn
 
 
 # ---------------------------------------------------------------------------
@@ -243,7 +249,15 @@ class SharedMLP(nn.Module):
 class PVConv(nn.Module):
     """Voxel branch (voxelize, two Conv3d + BN + LeakyReLU, devoxelize) plus
     point branch (SharedMLP), summed (pvcnn.py:504-576).  Inputs (features,
-    coords) or (features, coords, shared)."""
+    coords) or (features, coords, shared).  `fused` (on by default; no
+    parameter or buffer): in eval(), when no gradient is recorded (grad mode
+    off, or neither the grid nor a voxel_layers parameter requires grad) and
+    voxel_layers is Conv3d(k = 3, stride 1, padding 1) -> BatchNorm3d ->
+    LeakyReLU twice, optionally followed by SE3d, each triple runs as one
+    ops.voxel_conv3d with the BatchNorm folded from its running statistics
+    (SE3d stays torch); anything else, and `fused` off, is the torch
+    composition.  Forward hooks on voxel_layers or its children do not fire on
+    the fused path."""
 
     def __init__(self, in_channels, out_channels, kernel_size, resolution, with_se=False, normalize=True, eps=1e-6):
         super().__init__()
@@ -258,12 +272,57 @@ class PVConv(nn.Module):
             voxel_layers.append(SE3d(out_channels))
         self.voxel_layers = nn.Sequential(*voxel_layers)
         self.point_features = SharedMLP(in_channels, out_channels)
+        self.fused = True
+        self._packed = None  # (versions of voxel_layers' tensors, [(weight, bias, slope, packed)] * 2, SE3d or None)
+
+    def _triples(self):
+        """The two folded convolutions of voxel_layers with their packed
+        buffers and the trailing SE3d, rebuilt when one of the layers' tensors
+        was replaced or written to, a child was replaced, or a BatchNorm's eps
+        or a LeakyReLU's slope changed; None when the layers are no pattern
+        the kernel takes."""
+        key = tuple((t.data_ptr(), t._version)
+                    for t in list(self.voxel_layers.parameters()) + list(self.voxel_layers.buffers()))
+        # what the pattern, the fold and the activation read besides tensors
+        key += tuple((id(m), getattr(m, "eps", None), getattr(m, "negative_slope", None)) for m in self.voxel_layers)
+        hit = self._packed
+        if hit is None or hit[0] != key:
+            mods = list(self.voxel_layers)
+            se = mods.pop() if len(mods) == 7 and isinstance(mods[6], SE3d) else None
+            ok = len(mods) == 6
+            for conv, bn, act in zip(mods[0::3], mods[1::3], mods[2::3]) if ok else ():
+                ok = ok and isinstance(conv, nn.Conv3d) and isinstance(bn, nn.BatchNorm3d) and \
+                    isinstance(act, nn.LeakyReLU) and conv.kernel_size == (3, 3, 3) and conv.stride == (1, 1, 1) and \
+                    conv.padding == (1, 1, 1) and conv.dilation == (1, 1, 1) and conv.groups == 1 and \
+                    conv.padding_mode == "zeros" and conv.out_channels <= ops.VOXEL_CONV3D_COUT and \
+                    bn.running_mean is not None and bn.weight is not None and conv.weight.dtype == torch.float32
+            triples = None
+            if ok:
+                triples = []
+                with torch.no_grad():
+                    for conv, bn, act in zip(mods[0::3], mods[1::3], mods[2::3]):
+                        scale, shift = fold_bn(bn)
+                        w = (conv.weight * scale.view(-1, 1, 1, 1, 1)).contiguous()
+                        b = shift if conv.bias is None else conv.bias * scale + shift
+                        triples.append((w, b, float(act.negative_slope), ops.voxel_conv3d_pack(w, b)))
+            hit = self._packed = (key, triples, se)
+        return None if hit[1] is None else hit[1:]
+
+    def _voxel_branch(self, grid):
+        if self.fused and not self.training and not (torch.is_grad_enabled() and (
+                grid.requires_grad or any(p.requires_grad for p in self.voxel_layers.parameters()))):
+            hit = self._triples()
+            if hit is not None:
+                for w, b, slope, packed in hit[0]:
+                    grid = ops.voxel_conv3d(grid, w, b, slope, packed=packed)
+                return grid if hit[1] is None else hit[1](grid)
+        return self.voxel_layers(grid)
 
     def forward(self, inputs):
         features, coords = inputs[0], inputs[1]
         shared = inputs[2] if len(inputs) > 2 else None
         grid, _, devox = self.voxelization(features, coords, shared)
-        grid = self.voxel_layers(grid)
+        grid = self._voxel_branch(grid)
         keep = self.training or (torch.is_grad_enabled() and grid.requires_grad)
         voxel_features = trilinear_devoxelize(grid, devox.coords, self.resolution, keep, devox)
         return (voxel_features + self.point_features(features), *inputs[1:])

@@ -266,6 +266,17 @@ def _(unknown_feats, known_feats, dist2, idx, weights, biases):
     return known_feats.new_empty((dist2.shape[0], dist2.shape[1], weights[-1].shape[0]))
 
 
+@_op("voxel_conv3d")
+def voxel_conv3d(grid: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
+                 negative_slope: Optional[float] = None) -> Tensor:
+    return ops.voxel_conv3d(grid, weight, bias, negative_slope)
+
+
+@voxel_conv3d.register_fake
+def _(grid, weight, bias=None, negative_slope=None):
+    return grid.new_empty((grid.shape[0], weight.shape[0]) + tuple(grid.shape[2:]))
+
+
 # ----------------------------------------------------------------- sparse convolution
 @_op("sparse_conv")
 def sparse_conv(filters: Tensor, inp_features: Tensor, inp_importance: Optional[Tensor], neighbors_index: Tensor,
@@ -346,4 +357,4 @@ sparse_conv_transpose.register_autograd(_sct_backward, setup_context=_sct_setup)
 OPS = ("build_spatial_hash_table", "fixed_radius_search", "knn_search", "radius_search", "ragged_to_dense",
        "reduce_subarrays_sum", "voxelize", "furthest_point_sampling", "ball_query", "three_nn", "three_interpolate",
        "three_interpolate_grad", "nms", "sparse_conv", "sparse_conv_transpose", "trilinear_devoxelize_forward",
-       "trilinear_devoxelize_backward", "roi_pool", "fp_mlp")
+       "trilinear_devoxelize_backward", "roi_pool", "fp_mlp", "voxel_conv3d")

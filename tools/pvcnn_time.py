@@ -9,7 +9,20 @@ nominal 8 TB/s of an MI355X.  The torch rows: avg_voxelize as pvcnn.py:579-619
 (one scatter_add_ per channel, then the count), its autograd backward, a
 gather devoxelize and an index_add_ devoxelize backward.
 
-    python tools/pvcnn_time.py [--iters 20] [--skip-model] [--model-batch 8]
+``voxel_conv``: ops.voxel_conv3d (csrc/voxel_conv3d.hip) at the five layer
+shapes of the default model's voxel branch at B = 8, and at B = 1 for the
+r = 16 shapes, against the torch composition on the same tensors (Conv3d +
+eval BatchNorm3d + LeakyReLU, MIOpen; warmed up until it has picked its
+algorithm), the two alternating in one loop: medians with [min, max].
+``kernel_ms`` is the kernel's own time from the library's timing counter
+(voxel_conv3d), ``flop`` = 2 * 27 * Cin * Cout * B * r^3 and ``matrix_peak``
+= flop / kernel time over the 157.3 TF/s dense f32 matrix rate of one MI355X
+(256 CUs x 4 SIMDs x 4096 flop per 64-cycle v_mfma_f32_32x32x2_f32 at
+2.4 GHz, the figure tools/prcnn_time.py uses).  ``model.eval_fused`` /
+``eval_composed``: the eval forward under no_grad with PVConv.fused on and
+off, alternating.
+
+    python tools/pvcnn_time.py [--iters 20] [--skip-model] [--skip-ops] [--model-batch 8]
 """
 import argparse
 import json
@@ -23,6 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "open3d-ml_amd"))
 
 HBM_BYTES_PER_S = 8.0e12
+MFMA_F32_PEAK = 157.3e12  # dense f32 matrix rate of one MI355X
 
 
 def timed(fn, iters, warmup=3):
@@ -129,6 +143,90 @@ def ops_at(B, C, N, r, iters, dev):
     return out
 
 
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def spread(times):
+    return {"ms": round(statistics.median(times), 4), "min": round(min(times), 4), "max": round(max(times), 4)}
+
+
+CONV_SHAPES = [(8, 32, 9, 64), (8, 32, 64, 64), (8, 16, 64, 64), (8, 16, 64, 128), (8, 16, 128, 128),
+               (1, 16, 64, 64), (1, 16, 64, 128), (1, 16, 128, 128)]  # (B, r, Cin, Cout)
+
+
+def conv_at(B, r, cin, cout, iters, dev):
+    from o3dml_amd import _lib, ops
+    from o3dml_amd.point_transformer import fold_bn
+    torch.manual_seed(0)
+    seq = torch.nn.Sequential(torch.nn.Conv3d(cin, cout, 3, stride=1, padding=1),
+                              torch.nn.BatchNorm3d(cout, eps=1e-4), torch.nn.LeakyReLU(0.1, True))
+    seq[1].running_mean.normal_(0, 0.1)
+    seq[1].running_var.uniform_(0.5, 1.5)
+    seq = seq.to(dev).eval()
+    grid = torch.randn(B, cin, r, r, r, device=dev) * (torch.rand(B, 1, r, r, r, device=dev) > 1 / 3)
+    with torch.no_grad():
+        scale, shift = fold_bn(seq[1])
+        w = (seq[0].weight * scale.view(-1, 1, 1, 1, 1)).contiguous()
+        b = seq[0].bias * scale + shift
+        packed = ops.voxel_conv3d_pack(w, b)
+
+        def fused():
+            return ops.voxel_conv3d(grid, w, b, 0.1, packed=packed)
+
+        def composed():
+            return seq(grid.clone())  # the LeakyReLU is in place, as in the model
+
+        for _ in range(5):
+            fused()
+            composed()
+        ref = composed()
+        check = float((fused() - ref).abs().max() / ref.abs().max())
+        tf, tc = [], []
+        for _ in range(iters):
+            tf.append(event_ms(fused))
+            tc.append(event_ms(composed))
+        clone_ms = statistics.median([event_ms(lambda: grid.clone()) for _ in range(iters)])
+        lib = _lib.load()
+        lib.o3dml_timing_enable(1)
+        try:
+            lib.o3dml_timing_reset()
+            for _ in range(iters):
+                fused()
+            torch.cuda.synchronize()
+            ms, cnt = _lib.kernel_times(["voxel_conv3d"])["voxel_conv3d"]
+        finally:
+            lib.o3dml_timing_enable(0)
+    flop = 2 * 27 * cin * cout * B * r ** 3
+    kernel = ms / cnt
+    return {"B": B, "r": r, "cin": cin, "cout": cout, "flop": flop, "fused": spread(tf), "composed": spread(tc),
+            "composed_clone_ms": round(clone_ms, 4), "kernel_ms": round(kernel, 4),
+            "matrix_peak": round(flop / (kernel * 1e-3) / MFMA_F32_PEAK, 4), "check_rel": check}
+
+
+def model_eval_switch(m, run, iters):
+    from o3dml_amd.pvcnn import PVConv
+    blocks = [b for b in m.modules() if isinstance(b, PVConv)]
+    times = {True: [], False: []}
+    for fused in (True, False) * 2:  # warm-up of both settings
+        for b in blocks:
+            b.fused = fused
+        run()
+    for _ in range(iters):
+        for fused in (True, False):
+            for b in blocks:
+                b.fused = fused
+            times[fused].append(event_ms(run))
+    for b in blocks:
+        b.fused = True
+    return {"eval_fused": spread(times[True]), "eval_composed": spread(times[False])}
+
+
 def model_times(B, N, iters, dev):
     from o3dml_amd.pvcnn import PVCNN
     torch.manual_seed(0)
@@ -151,21 +249,26 @@ def model_times(B, N, iters, dev):
     m.train()
     t_train = timed(train, iters, warmup=2)
     m.eval()
-    return {"batch": B, "points": N, "train_step": row(t_train), "eval_forward": row(timed(evaluate, iters, warmup=2))}
+    res = {"batch": B, "points": N, "train_step": row(t_train), "eval_forward": row(timed(evaluate, iters, warmup=2))}
+    res.update(model_eval_switch(m, evaluate, max(iters, 10)))
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--skip-ops", action="store_true", help="leave out the point <-> voxel op rows")
     ap.add_argument("--model-batch", type=int, default=8)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pvcnn_time: no ROCm GPU is visible")
     dev = torch.device("cuda", 0)
     res = {"tool": "pvcnn_time", "device": torch.cuda.get_device_name(0), "iters": args.iters, "B": 8, "N": 40960}
-    res["C64_r32"] = ops_at(8, 64, 40960, 32, args.iters, dev)
-    res["C128_r16"] = ops_at(8, 128, 40960, 16, args.iters, dev)
+    if not args.skip_ops:
+        res["C64_r32"] = ops_at(8, 64, 40960, 32, args.iters, dev)
+        res["C128_r16"] = ops_at(8, 128, 40960, 16, args.iters, dev)
+    res["voxel_conv"] = [conv_at(*shape, args.iters, dev) for shape in CONV_SHAPES]
     if not args.skip_model:
         res["model"] = model_times(args.model_batch, 40960, max(3, args.iters // 4), dev)
     print(json.dumps(res))
