@@ -589,6 +589,28 @@ int64_t o3dml_voxel_conv3d_packed_size(int64_t Cin, int64_t Cout);
 int o3dml_voxel_conv3d(const float* grid, const float* packed, int64_t packed_len, int64_t B, int64_t Cin,
                        int64_t Cout, int64_t r, int has_slope, float negative_slope, float* out, void* stream);
 
+/* ---- dense voxel convolution, weight and bias gradients (the backward of the
+ * Conv3d above with respect to its parameters; the data gradient is
+ * o3dml_voxel_conv3d itself on the transposed, flipped weights).
+ *   grid      f32 [B,Cin,r,r,r]    the convolution's input
+ *   grad_out  f32 [B,Cout,r,r,r]   gradient w.r.t. the convolution's output
+ *   dweight   f32 [Cout,Cin,3,3,3] = sum over b, (x,y,z) of grad_out[b,co,x,y,z] *
+ *             grid[b,ci,x+dx-1,y+dy-1,z+dz-1], zeros outside the grid
+ *   dbias     f32 [Cout] or NULL   = sum over b and voxels of grad_out[b,co,.]
+ *   ws        device, ws_len floats >= o3dml_voxel_conv3d_wgrad_workspace_size(B,
+ *             Cin, Cout, r) (-1 when a limit is exceeded); needs no clearing
+ * The reduction over the B * r^3 voxels is split into S slabs of voxel boxes,
+ * S a function of (B, r, Cin, Cout) alone; a workgroup writes its slab's partial
+ * block to ws and a second kernel adds the slabs in ascending order.  Products
+ * exact f32 accumulated in f32 in one fixed order.  Every element of dweight
+ * and dbias is written (no memset needed); no atomics; run-to-run bitwise
+ * equal.  Inputs are finite.  Limits (status before any launch): B >= 0, r in
+ * 1..1290, Cin in 1..2^24, Cout in 1..512, ceil(Cin/32) * ceil(Cout/32) * 27648
+ * below 2^31. */
+int64_t o3dml_voxel_conv3d_wgrad_workspace_size(int64_t B, int64_t Cin, int64_t Cout, int64_t r);
+int o3dml_voxel_conv3d_wgrad(const float* grid, const float* grad_out, int64_t B, int64_t Cin, int64_t Cout,
+                             int64_t r, float* dweight, float* dbias, float* ws, int64_t ws_len, void* stream);
+
 /* ---- rotated BEV NMS: replaces open3d.ml.torch.ops.nms
  * (ml3d/torch/utils/objdet_helper.py:27, called by multiclass_nms :346 from
  * point_pillars.py:1005).  boxes f32 [N,5] (x1,y1,x2,y2,yaw), scores f32 [N];

@@ -187,6 +187,9 @@ SIGNATURES = {
     # voxel_conv3d.hip
     "o3dml_voxel_conv3d_packed_size": (c_i64, [c_i64, c_i64]),
     "o3dml_voxel_conv3d": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_f32, c_p, c_p]),
+    # voxel_conv3d_grad.hip
+    "o3dml_voxel_conv3d_wgrad_workspace_size": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "o3dml_voxel_conv3d_wgrad": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
     "o3dml_nms_workspace_size": (c_sz, [c_i64]),
     "o3dml_nms": (c_i32, [c_p, c_p, c_i64, c_f32, c_p, c_p, c_p, c_sz, c_p]),
     # box_iou.hip, box_iou_host.cpp

@@ -1127,16 +1127,8 @@ def voxel_conv3d_pack(weight, bias=None):
     return torch.cat([w.reshape(-1), torch.nn.functional.pad(b, (0, po))])
 
 
-def voxel_conv3d(grid, weight, bias=None, negative_slope=None, packed=None, out=None):
-    """Conv3d(Cin, Cout, 3, stride=1, padding=1) on a dense voxel grid with the
-    bias and an optional LeakyReLU in one kernel (csrc/voxel_conv3d.hip; PVConv
-    voxel_layers): grid float32 [B,Cin,r,r,r] contiguous, weight [Cout,Cin,3,3,3]
-    (a BatchNorm folded in by the caller), bias [Cout] or None -> float32
-    [B,Cout,r,r,r] = leaky(conv + bias), or conv + bias when negative_slope is
-    None.  `packed` takes voxel_conv3d_pack(weight, bias) from a caller that
-    keeps it between calls.  `out` takes a contiguous float32 [B,Cout,r,r,r] on
-    the GPU to write into (every element is written) and is returned.  Forward
-    only.  Not an Open3D name."""
+def _voxel_conv3d_run(grid, weight, bias=None, negative_slope=None, packed=None, out=None):
+    """voxel_conv3d without autograd: the argument checks and the launch."""
     cout, cin = _voxel_conv3d_weight(weight, bias)
     if not isinstance(grid, torch.Tensor) or grid.dtype != torch.float32 or grid.dim() != 5 or \
             len(set(grid.shape[2:])) != 1 or grid.shape[2] < 1:
@@ -1173,6 +1165,106 @@ def voxel_conv3d(grid, weight, bias=None, negative_slope=None, packed=None, out=
         _lib.call("o3dml_voxel_conv3d", ptr(g), ptr(packed), packed.numel(), B, cin, cout, r,
                   int(negative_slope is not None), float(negative_slope or 0.0), ptr(out), stream_handle(dev))
     return out if given else back_to(out, grid)
+
+
+def _voxel_grid(name, what, t):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 5 or \
+            len(set(t.shape[2:])) != 1 or t.shape[2] < 1 or t.shape[1] < 1:
+        raise RuntimeError(f"{name}: {what} must be float32 [B, C, r, r, r], got "
+                           f"{getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', []))}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name}: {what} must be contiguous")
+
+
+def voxel_conv3d_wgrad(grid, grad_out, bias=True):
+    """The weight and bias gradients of voxel_conv3d (csrc/voxel_conv3d_grad.hip):
+    grid float32 [B,Cin,r,r,r], grad_out [B,Cout,r,r,r] (the gradient of the
+    convolution's output, before any activation), both contiguous ->
+    (dweight [Cout,Cin,3,3,3], dbias [Cout] or None when `bias` is false).
+    Deterministic: fixed summation order, no atomics.  Not an Open3D name."""
+    _voxel_grid("voxel_conv3d_wgrad", "grid", grid)
+    _voxel_grid("voxel_conv3d_wgrad", "grad_out", grad_out)
+    B, cin, r = grid.shape[:3]
+    cout = grad_out.shape[1]
+    if (grad_out.shape[0], grad_out.shape[2]) != (B, r):
+        raise RuntimeError(f"voxel_conv3d_wgrad: grid {list(grid.shape)} and grad_out {list(grad_out.shape)} do not "
+                           "share B and r")
+    if cout > VOXEL_CONV3D_COUT:
+        raise RuntimeError(f"voxel_conv3d_wgrad: Cout = {cout} exceeds the limit {VOXEL_CONV3D_COUT}")
+    dev = gpu_device(grid, grad_out)
+    g, go = to_dev(grid.detach(), dev), to_dev(grad_out.detach(), dev)
+    n = int(_lib.load().o3dml_voxel_conv3d_wgrad_workspace_size(B, cin, cout, r))
+    if n < 0:
+        raise RuntimeError(f"voxel_conv3d_wgrad: {_lib.load().o3dml_last_error().decode()}")
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    dweight = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=dev)
+    dbias = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
+    _lib.call("o3dml_voxel_conv3d_wgrad", ptr(g), ptr(go), B, cin, cout, r, ptr(dweight), ptr(dbias), ptr(ws), n,
+              stream_handle(dev))
+    return back_to(dweight, grid), None if dbias is None else back_to(dbias, grid)
+
+
+def voxel_conv3d_grad_input(grad_out, weight, packed=None):
+    """The data gradient of voxel_conv3d: the forward kernel on the transposed,
+    flipped weights W'[ci,co,dx,dy,dz] = W[co,ci,2-dx,2-dy,2-dz].  grad_out
+    float32 [B,Cout,r,r,r] contiguous, weight [Cout,Cin,3,3,3] -> [B,Cin,r,r,r].
+    `packed` takes voxel_conv3d_pack(weight.flip(2, 3, 4).transpose(0, 1)
+    .contiguous()) from a caller that keeps it.  Cin sits on the kernel's Cout
+    side, so Cin <= 512.  Not an Open3D name."""
+    cout, cin = _voxel_conv3d_weight(weight, None)
+    if cin > VOXEL_CONV3D_COUT:
+        raise RuntimeError(f"voxel_conv3d_grad_input: Cin = {cin} exceeds the limit {VOXEL_CONV3D_COUT}")
+    _voxel_grid("voxel_conv3d_grad_input", "grad_out", grad_out)
+    if grad_out.shape[1] != cout:
+        raise RuntimeError(f"voxel_conv3d_grad_input: weight {list(weight.shape)} gives {cout} channels, grad_out "
+                           f"has {grad_out.shape[1]}")
+    wt = weight.detach().transpose(0, 1)
+    if packed is None:
+        wt = wt.flip(2, 3, 4).contiguous()
+    return _voxel_conv3d_run(grad_out, wt, None, None, packed)
+
+
+class _VoxelConv3d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, grid, weight, bias, negative_slope, packed):
+        out = _voxel_conv3d_run(grid, weight, bias, negative_slope, packed)
+        ctx.slope = negative_slope
+        ctx.save_for_backward(grid, weight, out if negative_slope is not None else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        grid, weight, out = ctx.saved_tensors
+        if ctx.slope is not None:  # the LeakyReLU's derivative from the output's sign (slope > 0)
+            grad_out = torch.where(out > 0, grad_out, grad_out * ctx.slope)
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        dgrid = voxel_conv3d_grad_input(grad_out, weight) if need[0] else None
+        dweight, dbias = voxel_conv3d_wgrad(grid, grad_out, bias=need[2]) if need[1] or need[2] else (None, None)
+        return dgrid, dweight if need[1] else None, dbias, None, None
+
+
+def voxel_conv3d(grid, weight, bias=None, negative_slope=None, packed=None, out=None):
+    """Conv3d(Cin, Cout, 3, stride=1, padding=1) on a dense voxel grid with the
+    bias and an optional LeakyReLU in one kernel (csrc/voxel_conv3d.hip; PVConv
+    voxel_layers): grid float32 [B,Cin,r,r,r] contiguous, weight [Cout,Cin,3,3,3]
+    (a BatchNorm folded in by the caller), bias [Cout] or None -> float32
+    [B,Cout,r,r,r] = leaky(conv + bias), or conv + bias when negative_slope is
+    None.  `packed` takes voxel_conv3d_pack(weight, bias) from a caller that
+    keeps it between calls.  `out` takes a contiguous float32 [B,Cout,r,r,r] on
+    the GPU to write into (every element is written) and is returned.
+    Differentiable once with respect to grid, weight and bias when grad mode is
+    on and one of them requires grad (voxel_conv3d_grad_input,
+    voxel_conv3d_wgrad; then negative_slope must be positive and `out` None);
+    no gradient reaches `packed`.  Not an Open3D name."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (grid, weight, bias)):
+        if out is not None:
+            raise RuntimeError("voxel_conv3d: out cannot be given when a gradient is recorded")
+        if negative_slope is not None and not negative_slope > 0:
+            raise RuntimeError(f"voxel_conv3d: the gradient needs negative_slope > 0, got {negative_slope}")
+        return _VoxelConv3d.apply(grid, weight, bias, negative_slope, packed)
+    return _voxel_conv3d_run(grid, weight, bias, negative_slope, packed, out)
 
 
 # ---------------------------------------------------------------------------

@@ -257,7 +257,14 @@ class PVConv(nn.Module):
     ops.voxel_conv3d with the BatchNorm folded from its running statistics
     (SE3d stays torch); anything else, and `fused` off, is the torch
     composition.  Forward hooks on voxel_layers or its children do not fire on
-    the fused path."""
+    the fused path.  `fused_grad` (off by default; no parameter or buffer):
+    in train(), or when a gradient is recorded, and voxel_layers is that same
+    pattern with at most 512 input channels, each Conv3d runs as
+    ops.voxel_conv3d on its raw weights, forward and backward on the kernels
+    (csrc/voxel_conv3d_grad.hip), followed by the block's own BatchNorm3d and
+    LeakyReLU modules (batch statistics, running-statistic updates and hooks on
+    those two as in the composition; hooks on the Conv3d or on voxel_layers do
+    not fire)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, resolution, with_se=False, normalize=True, eps=1e-6):
         super().__init__()
@@ -273,7 +280,23 @@ class PVConv(nn.Module):
         self.voxel_layers = nn.Sequential(*voxel_layers)
         self.point_features = SharedMLP(in_channels, out_channels)
         self.fused = True
+        self.fused_grad = False
         self._packed = None  # (versions of voxel_layers' tensors, [(weight, bias, slope, packed)] * 2, SE3d or None)
+
+    def _pattern(self):
+        """(the six modules of the two Conv3d -> BatchNorm3d -> LeakyReLU
+        triples, the trailing SE3d or None) when voxel_layers is the pattern
+        the kernels take, else (None, None)."""
+        mods = list(self.voxel_layers)
+        se = mods.pop() if len(mods) == 7 and isinstance(mods[6], SE3d) else None
+        ok = len(mods) == 6
+        for conv, bn, act in zip(mods[0::3], mods[1::3], mods[2::3]) if ok else ():
+            ok = ok and isinstance(conv, nn.Conv3d) and isinstance(bn, nn.BatchNorm3d) and \
+                isinstance(act, nn.LeakyReLU) and conv.kernel_size == (3, 3, 3) and conv.stride == (1, 1, 1) and \
+                conv.padding == (1, 1, 1) and conv.dilation == (1, 1, 1) and conv.groups == 1 and \
+                conv.padding_mode == "zeros" and conv.out_channels <= ops.VOXEL_CONV3D_COUT and \
+                bn.running_mean is not None and bn.weight is not None and conv.weight.dtype == torch.float32
+        return (mods, se) if ok else (None, None)
 
     def _triples(self):
         """The two folded convolutions of voxel_layers with their packed
@@ -287,17 +310,9 @@ class PVConv(nn.Module):
         key += tuple((id(m), getattr(m, "eps", None), getattr(m, "negative_slope", None)) for m in self.voxel_layers)
         hit = self._packed
         if hit is None or hit[0] != key:
-            mods = list(self.voxel_layers)
-            se = mods.pop() if len(mods) == 7 and isinstance(mods[6], SE3d) else None
-            ok = len(mods) == 6
-            for conv, bn, act in zip(mods[0::3], mods[1::3], mods[2::3]) if ok else ():
-                ok = ok and isinstance(conv, nn.Conv3d) and isinstance(bn, nn.BatchNorm3d) and \
-                    isinstance(act, nn.LeakyReLU) and conv.kernel_size == (3, 3, 3) and conv.stride == (1, 1, 1) and \
-                    conv.padding == (1, 1, 1) and conv.dilation == (1, 1, 1) and conv.groups == 1 and \
-                    conv.padding_mode == "zeros" and conv.out_channels <= ops.VOXEL_CONV3D_COUT and \
-                    bn.running_mean is not None and bn.weight is not None and conv.weight.dtype == torch.float32
+            mods, se = self._pattern()
             triples = None
-            if ok:
+            if mods is not None:
                 triples = []
                 with torch.no_grad():
                     for conv, bn, act in zip(mods[0::3], mods[1::3], mods[2::3]):
@@ -309,13 +324,22 @@ class PVConv(nn.Module):
         return None if hit[1] is None else hit[1:]
 
     def _voxel_branch(self, grid):
-        if self.fused and not self.training and not (torch.is_grad_enabled() and (
-                grid.requires_grad or any(p.requires_grad for p in self.voxel_layers.parameters()))):
-            hit = self._triples()
+        recorded = torch.is_grad_enabled() and (
+            grid.requires_grad or any(p.requires_grad for p in self.voxel_layers.parameters()))
+        if not self.training and not recorded:
+            hit = self._triples() if self.fused else None
             if hit is not None:
                 for w, b, slope, packed in hit[0]:
                     grid = ops.voxel_conv3d(grid, w, b, slope, packed=packed)
                 return grid if hit[1] is None else hit[1](grid)
+        elif self.fused_grad:
+            # batch statistics or recorded gradients: the convolution and its backward on the kernels (raw
+            # weights, no activation), the block's own BatchNorm3d and LeakyReLU modules after each
+            mods, se = self._pattern()
+            if mods is not None and mods[0].in_channels <= ops.VOXEL_CONV3D_COUT:
+                for conv, bn, act in zip(mods[0::3], mods[1::3], mods[2::3]):
+                    grid = act(bn(ops.voxel_conv3d(grid, conv.weight, conv.bias)))
+                return grid if se is None else se(grid)
         return self.voxel_layers(grid)
 
     def forward(self, inputs):

@@ -22,6 +22,19 @@ algorithm), the two alternating in one loop: medians with [min, max].
 ``eval_composed``: the eval forward under no_grad with PVConv.fused on and
 off, alternating.
 
+``voxel_conv_grad``: at the same eight shapes, ops.voxel_conv3d_wgrad
+(csrc/voxel_conv3d_grad.hip; its kernels' own times from the counters
+voxel_conv3d_wgrad and voxel_conv3d_wgrad_reduce, ``wgrad_matrix_peak`` = flop
+/ wgrad kernel time over the same 157.3 TF/s) and ops.voxel_conv3d_grad_input
+against torch's conv3d backward through autograd (weight, bias and input
+gradients in one call, MIOpen), alternating on the same tensors.
+``model.train_fused_grad`` / ``train_composed``: the train step with
+PVConv.fused_grad on and off, alternating; ``composed_profile``: one off step
+under torch.profiler, the device time of the 5-D aten::convolution_backward
+calls as a share of the step; ``train_fused_grad_differing``: the parameters
+whose gradients differ bitwise between two backward passes from the same state
+with fused_grad on (the Conv1d weights, whose gradient is MIOpen's).
+
     python tools/pvcnn_time.py [--iters 20] [--skip-model] [--skip-ops] [--model-batch 8]
 """
 import argparse
@@ -209,6 +222,105 @@ def conv_at(B, r, cin, cout, iters, dev):
             "matrix_peak": round(flop / (kernel * 1e-3) / MFMA_F32_PEAK, 4), "check_rel": check}
 
 
+def conv_grad_at(B, r, cin, cout, iters, dev):
+    """The convolution's backward at one layer shape: ops.voxel_conv3d_wgrad and
+    ops.voxel_conv3d_grad_input against torch's conv3d backward through
+    autograd (weight, bias and input gradients; MIOpen), alternating."""
+    from o3dml_amd import _lib, ops
+    torch.manual_seed(0)
+    grid = torch.randn(B, cin, r, r, r, device=dev) * (torch.rand(B, 1, r, r, r, device=dev) > 1 / 3)
+    gout = torch.randn(B, cout, r, r, r, device=dev)
+    w = (torch.randn(cout, cin, 3, 3, 3, device=dev) / (27 * cin) ** 0.5).requires_grad_()
+    b = torch.zeros(cout, device=dev, requires_grad=True)
+    gin = grid.clone().requires_grad_()
+    packed_t = ops.voxel_conv3d_pack(w.detach().flip(2, 3, 4).transpose(0, 1).contiguous())
+    y = torch.nn.functional.conv3d(gin, w, b, padding=1)
+
+    def wgrad():
+        return ops.voxel_conv3d_wgrad(grid, gout)
+
+    def dgrad():
+        return ops.voxel_conv3d_grad_input(gout, w, packed=packed_t)
+
+    def miopen():
+        return torch.autograd.grad(y, (gin, w, b), gout, retain_graph=True)
+
+    for _ in range(5):
+        wgrad(), dgrad(), miopen()
+    ref = miopen()
+    rel = lambda a, c: float((a - c).abs().max() / c.abs().max())  # noqa: E731
+    check = {"dx": rel(dgrad(), ref[0]), "dw": rel(wgrad()[0], ref[1]), "db": rel(wgrad()[1], ref[2])}
+    tw, td, tm = [], [], []
+    for _ in range(iters):
+        tw.append(event_ms(wgrad))
+        td.append(event_ms(dgrad))
+        tm.append(event_ms(miopen))
+    names = ["voxel_conv3d_wgrad", "voxel_conv3d_wgrad_reduce"]
+    lib = _lib.load()
+    lib.o3dml_timing_enable(1)
+    try:
+        lib.o3dml_timing_reset()
+        for _ in range(iters):
+            wgrad()
+        torch.cuda.synchronize()
+        kt = _lib.kernel_times(names)
+    finally:
+        lib.o3dml_timing_enable(0)
+    flop = 2 * 27 * cin * cout * B * r ** 3
+    kernel = kt[names[0]][0] / kt[names[0]][1]
+    return {"B": B, "r": r, "cin": cin, "cout": cout, "flop": flop, "wgrad": spread(tw), "dgrad": spread(td),
+            "torch_backward": spread(tm), "wgrad_kernel_ms": round(kernel, 4),
+            "wgrad_reduce_kernel_ms": round(kt[names[1]][0] / kt[names[1]][1], 4),
+            "wgrad_matrix_peak": round(flop / (kernel * 1e-3) / MFMA_F32_PEAK, 4), "check_rel": check}
+
+
+def model_train_switch(m, train, iters):
+    """The train step with PVConv.fused_grad on and off, alternating, and the
+    off step's time inside convolution backward (torch.profiler, the device
+    time of the 5-D aten::convolution_backward calls over the step's median)."""
+    from o3dml_amd.pvcnn import PVConv
+    from torch.profiler import ProfilerActivity, profile
+    blocks = [b for b in m.modules() if isinstance(b, PVConv)]
+    times = {True: [], False: []}
+    for on in (True, False) * 2:
+        for b in blocks:
+            b.fused_grad = on
+        train()
+    for _ in range(iters):
+        for on in (True, False):
+            for b in blocks:
+                b.fused_grad = on
+            times[on].append(event_ms(train))
+    # two backward passes from the same state with fused_grad on: the parameters whose gradients differ bitwise
+    for b in blocks:
+        b.fused_grad = True
+    grads = []
+    for _ in range(2):
+        torch.manual_seed(1)  # the Dropout masks
+        train(step=False)
+        grads.append({k: p.grad.clone() for k, p in m.named_parameters()})
+    for b in blocks:
+        b.fused_grad = False
+    res = {"train_fused_grad": spread(times[True]), "train_composed": spread(times[False]),
+           "train_fused_grad_differing": [k for k in grads[0] if not torch.equal(grads[0][k], grads[1][k])]}
+    try:  # the off step under the profiler, last: a profiler that fails to start costs only this field
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], record_shapes=True) as prof:
+            train()
+            torch.cuda.synchronize()
+        events = prof.key_averages(group_by_input_shape=True)
+        dev_time = lambda e: getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0)  # noqa: E731
+        conv3d = lambda e, key: e.key == key and e.input_shapes and len(e.input_shapes[0]) == 5  # noqa: E731
+        conv_bwd = sum(dev_time(e) for e in events if conv3d(e, "aten::convolution_backward")) * 1e-3
+        conv_fwd = sum(dev_time(e) for e in events if conv3d(e, "aten::convolution")) * 1e-3
+        res["composed_profile"] = {"conv3d_backward_ms": round(conv_bwd, 3), "conv3d_forward_ms": round(conv_fwd, 3),
+                                   "conv3d_backward_share_of_step": round(conv_bwd / res["train_composed"]["ms"], 4)}
+    except Exception as e:  # noqa: BLE001
+        res["composed_profile"] = {"error": repr(e)}
+        print(f"pvcnn_time: no profile of the composed step, conv3d_backward_share_of_step is missing: {e!r}",
+              file=sys.stderr)
+    return res
+
+
 def model_eval_switch(m, run, iters):
     from o3dml_amd.pvcnn import PVConv
     blocks = [b for b in m.modules() if isinstance(b, PVConv)]
@@ -236,11 +348,12 @@ def model_times(B, N, iters, dev):
     labels = torch.randint(0, 13, (B * N,), device=dev)
     opt = torch.optim.Adam(m.parameters(), 1e-3)
 
-    def train():
+    def train(step=True):
         opt.zero_grad(set_to_none=True)
         loss = torch.nn.functional.cross_entropy(m({"point": pts, "feat": feat}).reshape(-1, 13), labels)
         loss.backward()
-        opt.step()
+        if step:
+            opt.step()
 
     def evaluate():
         with torch.no_grad():
@@ -248,8 +361,10 @@ def model_times(B, N, iters, dev):
 
     m.train()
     t_train = timed(train, iters, warmup=2)
+    switch = model_train_switch(m, train, max(iters, 5))
     m.eval()
     res = {"batch": B, "points": N, "train_step": row(t_train), "eval_forward": row(timed(evaluate, iters, warmup=2))}
+    res.update(switch)
     res.update(model_eval_switch(m, evaluate, max(iters, 10)))
     return res
 
@@ -269,6 +384,7 @@ def main():
         res["C64_r32"] = ops_at(8, 64, 40960, 32, args.iters, dev)
         res["C128_r16"] = ops_at(8, 128, 40960, 16, args.iters, dev)
     res["voxel_conv"] = [conv_at(*shape, args.iters, dev) for shape in CONV_SHAPES]
+    res["voxel_conv_grad"] = [conv_grad_at(*shape, args.iters, dev) for shape in CONV_SHAPES]
     if not args.skip_model:
         res["model"] = model_times(args.model_batch, 40960, max(3, args.iters // 4), dev)
     print(json.dumps(res))
